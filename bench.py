@@ -13,13 +13,21 @@ Driver contract:
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
       --master-addr 127.0.0.1 bench.py --gpus N --steps K --warmup W
 Rank 0 prints one JSON line with the aggregate rows/sec.
+
+A plain run sets up, warms up, times the steps and prints the result line.
+--dump-outputs DIR also writes the last timed step's result as .npy arrays;
+--full is reserved for anything measured beyond the headline figure.
 """
 
 import argparse
+import hashlib
 import json
 import os
+import shutil
 import sys
+import tempfile
 import time
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
@@ -120,6 +128,97 @@ def run_query(bpd, trips_table, weather_df):
     return shard
 
 
+def trips_parquet_dir(n_local, rank, world, device):
+    """Where this rank's trips shard lives as parquet.  The shard is a pure
+    function of this file (seeds, schema, writer settings), the torch
+    version and the shard's place in the run, so the name is a hash of
+    those and a later run with the same arguments finds the files of an
+    earlier one instead of encoding 22 GB again.  Entries of the scratch
+    directory that nobody wrote or reused for six hours are removed."""
+    with open(os.path.abspath(__file__), "rb") as f:
+        h = hashlib.sha1(f.read())
+    h.update(f"|{torch.__version__}|{device}|{n_local}|{rank}|{world}"
+             .encode())
+    base = os.path.join(tempfile.gettempdir(), f"bodo_bench_pq_{os.getuid()}")
+    os.makedirs(base, exist_ok=True)
+    for name in os.listdir(base):
+        old = os.path.join(base, name)
+        try:
+            if time.time() - os.path.getmtime(old) > 6 * 3600:
+                shutil.rmtree(old, ignore_errors=True)
+        except OSError:
+            pass
+    return os.path.join(base, f"trips_{h.hexdigest()[:16]}")
+
+
+def write_trips_parquet(trips, pq_dir, n_threads=12):
+    """Write the shard as a directory of snappy parquet files, one per
+    2**24-row chunk (two 2**23-row row groups each), encoded by a thread
+    pool.  The row groups, and their order under the reader's sorted file
+    listing, are the ones a single sequential writer produces; only the
+    encoding runs in parallel.  Host staging stays bounded at one chunk
+    (~0.6 GB) per thread.  The files appear under pq_dir's final name only
+    once all are complete, so a reader never meets a partial shard."""
+    import pyarrow.parquet as pq
+
+    from bodo_amd import ops as _ops
+
+    final_dir, pq_dir = pq_dir, f"{pq_dir}.tmp{os.getpid()}"
+    shutil.rmtree(pq_dir, ignore_errors=True)
+    os.makedirs(pq_dir)
+    CHUNK = 1 << 24
+
+    def write_chunk(i):
+        s = i * CHUNK
+        at = _ops.slice_table(trips, s, min(s + CHUNK, len(trips))) \
+            .to_device("cpu").to_arrow()
+        path = os.path.join(pq_dir, f"part-{i:05d}.parquet")
+        with pq.ParquetWriter(path, at.schema, compression="SNAPPY",
+                              use_dictionary=["hvfhs_license_num"]) as writer:
+            writer.write_table(at, row_group_size=1 << 23)
+        return os.path.getsize(path)
+
+    n_chunks = max(1, -(-len(trips) // CHUNK))
+    with ThreadPoolExecutor(max_workers=n_threads) as pool:
+        n_bytes = sum(pool.map(write_chunk, range(n_chunks)))
+    try:
+        os.rename(pq_dir, final_dir)
+    except OSError:  # another run finished the same shard first: use theirs
+        shutil.rmtree(pq_dir, ignore_errors=True)
+    return n_bytes
+
+
+def dump_outputs(shard, out_dir, rank, world, max_rows=1 << 19):
+    """Write the last timed step's result shard as <column>.npy (float64).
+    A result larger than max_rows is cut to a fixed seeded sample of its
+    rows (ascending, so the sort order is kept); string columns are stored
+    as the rank of each value among the sample's sorted distinct values.
+    num_rows.npy holds the full shard length."""
+    import pandas as pd
+
+    from bodo_amd import ops as _ops
+
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(shard)
+    if n > max_rows:
+        idx = np.sort(np.random.default_rng(2023).choice(
+            n, max_rows, replace=False))
+        shard = _ops.take_table(
+            shard, torch.from_numpy(idx).to(shard.device))
+    df = shard.to_device("cpu").to_pandas()
+    suffix = "" if world == 1 else f"_rank{rank}"
+    arrays = {"num_rows": np.array([n], dtype=np.float64)}
+    for name in df.columns:
+        col = df[name]
+        if not (pd.api.types.is_numeric_dtype(col.dtype)
+                or pd.api.types.is_bool_dtype(col.dtype)):
+            col = col.astype(str)
+            col = pd.Categorical(col, categories=sorted(col.unique())).codes
+        arrays[name] = np.asarray(col, dtype=np.float64)
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), arr)
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
@@ -132,6 +231,14 @@ def main():
                         "with on-GPU decode (BASELINE config 2; the default)")
     p.add_argument("--no-parquet", dest="parquet", action="store_false",
                    help="skip parquet IO: query in-HBM synthetic shards")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the last step's result "
+                        "as DIR/<column>.npy (float64; a fixed seeded row "
+                        "sample when the result is large)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the measurements beyond the headline "
+                        "figure (none at present: a plain run already does "
+                        "only setup, warmup, the timed steps and the result)")
     args = p.parse_args()
 
     import bodo_amd  # noqa: F401  (inits process group under torchrun)
@@ -151,7 +258,6 @@ def main():
     n_total = args.rows
     base, rem = divmod(n_total, world)
     n_local = base + (1 if rank < rem else 0)
-    trips = make_trips_shard(n_local, rank, device)
     weather = make_weather()
 
     def log(msg):
@@ -160,39 +266,28 @@ def main():
                   file=sys.stderr, flush=True)
 
     T0 = time.perf_counter()
-    log(f"generated {n_local} rows on {device}")
+    trips = None
     pq_path = None
     if args.parquet:
-        # write this rank's shard as snappy parquet (untimed; the realistic
-        # on-disk layout), then each step re-reads it with the on-GPU
-        # decoder before the query
-        import pyarrow.parquet as pq
-
-        from bodo_amd import ops as _ops
-
-        os.makedirs("/tmp/bodo_bench_pq", exist_ok=True)
-        pq_path = f"/tmp/bodo_bench_pq/trips_rank{rank}.parquet"
-        # chunked write keeps the host staging bounded at ~1.3 GB even for
-        # the full 1B-row shard
-        CHUNK = 1 << 25
-        writer = None
-        for s in range(0, len(trips), CHUNK):
-            at = _ops.slice_table(trips, s, min(s + CHUNK, len(trips))) \
-                .to_device("cpu").to_arrow()
-            if writer is None:
-                writer = pq.ParquetWriter(
-                    pq_path, at.schema, compression="SNAPPY",
-                    use_dictionary=["hvfhs_license_num"])
-            writer.write_table(at, row_group_size=1 << 23)
-            del at
-        writer.close()
+        # this rank's shard as snappy parquet (untimed; the realistic
+        # on-disk layout); each step re-reads it with the on-GPU decoder
+        # before the query
+        pq_path = trips_parquet_dir(n_local, rank, world, device)
+    if pq_path is not None and os.path.isdir(pq_path):
+        os.utime(pq_path)  # in use: keep it from the age sweep
+        log(f"parquet reused: {pq_path}")
+    else:
+        trips = make_trips_shard(n_local, rank, device)
+        log(f"generated {n_local} rows on {device}")
+    if pq_path is not None and trips is not None:
+        pq_bytes = write_trips_parquet(trips, pq_path)
         # the generated device table is only the write source; freeing it
         # returns ~37 GB of HBM to the query working set at 1B rows
         del trips
         trips = None
         if on_gpu:
             torch.cuda.empty_cache()
-        log(f"parquet written: {os.path.getsize(pq_path)} bytes")
+        log(f"parquet written: {pq_bytes} bytes")
 
     def read_trips():
         if pq_path is None:
@@ -212,7 +307,7 @@ def main():
 
     def one_step():
         shard = run_query(bpd, read_trips(), weather)
-        return sum(comm.allgather_obj(len(shard)))
+        return sum(comm.allgather_obj(len(shard))), shard
 
     for _ in range(args.warmup):
         one_step()
@@ -222,8 +317,12 @@ def main():
         torch.cuda.synchronize()
     t0 = time.perf_counter()
     out_rows = 0
-    for _ in range(args.steps):
-        out_rows = one_step()
+    last_shard = None
+    for i in range(args.steps):
+        out_rows, shard = one_step()
+        if i == args.steps - 1:
+            last_shard = shard
+        del shard
         log("timed step done")
     if on_gpu:
         torch.cuda.synchronize()
@@ -232,6 +331,9 @@ def main():
     elapsed = max(comm.allgather_obj(elapsed))
     ms_per_step = elapsed / args.steps * 1000.0
     rows_per_sec = n_total / (elapsed / args.steps)
+    if args.dump_outputs and last_shard is not None:
+        dump_outputs(last_shard, args.dump_outputs, rank, world)
+        log(f"outputs written to {args.dump_outputs}")
     if rank == 0:
         print(json.dumps({
             "metric": "nyc_taxi_q1_rows_per_sec",
