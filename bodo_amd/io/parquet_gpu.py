@@ -2,13 +2,15 @@
 cudf::io::read_parquet in bodo/pandas/physical/gpu_read_parquet.h).
 
 Host side: footer metadata (pyarrow), raw column-chunk byte ranges read from
-disk, page headers parsed with a minimal Thrift compact-protocol reader, and
-RLE run boundaries scanned (runs are few).  Device side: PLAIN value pages
-are zero-copy-viewed into HBM; RLE_DICTIONARY index pages expand through the
-hand-written rle_expand kernel; dictionary values become the column
-dictionary.  Supported: uncompressed v1 data pages, all-valid values
-(no nulls), PLAIN numeric + RLE_DICTIONARY (any type).  Unsupported chunks
-fall back to the host Arrow decoder per column chunk.
+disk into pinned staging, page headers parsed in C++ (Thrift compact
+protocol), the small dictionary page decoded on the host.  Device side, per
+column chunk: snappy (or uncompressed) v1 data pages decompress one wave per
+page, definition levels expand to a validity mask (nullable columns),
+then PLAIN fixed-width values, PLAIN BYTE_ARRAY strings or RLE_DICTIONARY
+codes are assembled into a Column.  The pipelined shard reader decompresses
+the pages of every column chunk of a few row groups in one launch.  Chunks
+outside this path (other codecs, v2 pages, BOOLEAN/INT96/FIXED_LEN, mixed
+plain/dict) take the older per-page route and then the host Arrow decoder.
 """
 
 from __future__ import annotations
@@ -193,6 +195,23 @@ _PAGEMETA_DT = np.dtype([
 _PQF_HAS_DEF = 1
 _PQF_SNAPPY = 2
 
+# page table entry of K.pq_decompress_multi: absolute device addresses
+_PAGEPTR_DT = np.dtype([
+    ("src", np.uint64), ("dst", np.uint64), ("src_len", np.int32),
+    ("dst_len", np.int32), ("flags", np.int32), ("pad", np.int32),
+])
+# row groups whose column chunks share one decompress launch in the
+# pipelined reader (1..32 measured: profiles/decode_parallel_snappy.md)
+_GROUP_ROW_GROUPS = 16
+
+
+class _Prepared:
+    """A column chunk between the two halves of the batched decode: page
+    table built and scratch allocated, pages not yet decompressed."""
+
+    __slots__ = ("mode", "dict_vals", "metas", "metas_dev", "n_pages",
+                 "src_dev", "scratch", "val_off", "total_nv")
+
 
 def _chunk_range(chunk_meta):
     start = chunk_meta.dictionary_page_offset
@@ -257,6 +276,18 @@ class _ChunkReader:
         return col
 
     def _decode_batched(self, device, field: pa.Field) -> Optional[Column]:
+        prep = self._prepare_batched(device)
+        if prep is None:
+            return None
+        import bodo_amd_kernels as K
+
+        K.pq_decompress(prep.src_dev, prep.metas_dev, prep.n_pages,
+                        prep.scratch)
+        return self._finish_batched(prep, device, field)
+
+    def _prepare_batched(self, device) -> Optional[_Prepared]:
+        """First half: headers, dictionary page, page table, scratch.
+        None when the chunk is outside the batched path."""
         if torch.device(device).type != "cuda" and not FORCE_BATCHED:
             return None  # batched kernels are device-only (tests simulate)
         comp = self.meta.compression
@@ -339,8 +370,22 @@ class _ChunkReader:
         metas_dev = torch.from_numpy(metas.view(np.uint8)).to(device)
         scratch_size = int(((d_usize + 7) & ~7).sum()) + 16
         scratch = torch.empty(scratch_size, dtype=torch.uint8, device=device)
-        K.pq_decompress(src_dev, metas_dev, n_pages, scratch)
+        prep = _Prepared()
+        prep.mode, prep.dict_vals = mode, dict_vals
+        prep.metas, prep.metas_dev, prep.n_pages = metas, metas_dev, n_pages
+        prep.src_dev, prep.scratch = src_dev, scratch
+        prep.val_off, prep.total_nv = val_off, total_nv
+        return prep
 
+    def _finish_batched(self, prep: _Prepared, device,
+                        field: pa.Field) -> Optional[Column]:
+        """Second half, once prep.scratch holds the decompressed pages:
+        def levels, then codes / strings / fixed-width values."""
+        import bodo_amd_kernels as K
+
+        mode, dict_vals = prep.mode, prep.dict_vals
+        metas_dev, n_pages, scratch = prep.metas_dev, prep.n_pages, prep.scratch
+        val_off, total_nv = prep.val_off, prep.total_nv
         mask_t = None
         n_valid = None
         vdo = None
@@ -614,8 +659,10 @@ def _read_pieces_pipelined(my, columns, ctx) -> Optional[Table]:
     staging buffers (`f.readinto`, no intermediate copy); the consumer
     parses page headers (C++), snips the small dictionary page, issues the
     async H2D copy and releases the slot for reuse once the copy's event
-    fires.  Disk read, PCIe upload and decode kernels of different chunks
-    overlap (reference role: bodo/io/parquet_reader.cpp prefetch +
+    fires.  Chunks are decoded in groups of _GROUP_ROW_GROUPS row groups:
+    each is prepared as it arrives, one decompress launch covers the pages
+    of the whole group, then each chunk is finished.  Disk read overlaps
+    PCIe upload and decode kernels of other chunks (reference role: bodo/io/parquet_reader.cpp prefetch +
     _io_cpu_thread_pool.cpp)."""
     import time
     from concurrent.futures import ThreadPoolExecutor
@@ -659,9 +706,9 @@ def _read_pieces_pipelined(my, columns, ctx) -> Optional[Table]:
 
     def fetch(idx):
         fp, rg, cm, field, start, size, first, names = items[idx]
-        t0 = time.perf_counter()
         i = idx % _NSLOTS
         sems[i].acquire()
+        t0 = time.perf_counter()  # read time proper: not the slot wait
         s = slots[i]
         if s["ev"] is not None:
             s["ev"].synchronize()  # previous H2D out of this slot is done
@@ -677,24 +724,88 @@ def _read_pieces_pipelined(my, columns, ctx) -> Optional[Table]:
         return i
 
     ex = ThreadPoolExecutor(max_workers=_NSLOTS)
-    inflight: List[torch.cuda.Event] = []
-    try:
-        futs = [ex.submit(fetch, k) for k in range(len(items))]
-        rg_tables: List[Table] = []
+    # (event, chunk count) per flushed group or per-chunk fallback decode
+    inflight: List[Tuple[torch.cuda.Event, int]] = []
+    # chunks of the current group: [name, names-of-its-row-group, first,
+    # reader, field, prepared-or-None, Column-or-None]
+    group: list = []
+    group_rgs = 0
+    rg_tables: List[Table] = []
+
+    def flush():
+        """One decompress launch for every prepared chunk of the group,
+        then the second half of each chunk's decode, then the tables."""
+        nonlocal group, group_rgs
+        if not group:
+            return True
+        t0 = time.perf_counter()
+        preps = [e[5] for e in group if e[5] is not None]
+        if preps:
+            tbl = np.zeros(sum(p.n_pages for p in preps), dtype=_PAGEPTR_DT)
+            at = 0
+            for p in preps:
+                v = tbl[at:at + p.n_pages]
+                v["src"] = p.src_dev.data_ptr() + p.metas["src_off"]
+                v["dst"] = p.scratch.data_ptr() + p.metas["dst_off"]
+                v["src_len"] = p.metas["src_len"]
+                v["dst_len"] = p.metas["dst_len"]
+                v["flags"] = p.metas["flags"] & _PQF_SNAPPY
+                at += p.n_pages
+            tbl_dev = torch.from_numpy(tbl.view(np.uint8)).to(device)
+            K.pq_decompress_multi(tbl_dev, len(tbl))
+        for e in group:
+            if e[5] is None:
+                continue
+            reader, field = e[3], e[4]
+            try:
+                col = reader._finish_batched(e[5], device, field)
+            except Exception:
+                col = None
+            e[5] = None  # drop the chunk's source and scratch tensors
+            if col is not None:
+                STATS["batched"] += 1
+            else:  # today's per-chunk route, from the top
+                col = reader.decode_column(device, field)
+            e[6] = col
+        if preps:
+            done = torch.cuda.Event()
+            done.record()
+            inflight.append((done, len(preps)))
+        STATS["t_decode"] = STATS.get("t_decode", 0.0) + \
+            time.perf_counter() - t0
+        ok = all(e[6] is not None for e in group)
         cur_cols: List[Column] = []
         cur_names: List[str] = []
+        rg_names = None
+        for e in group:
+            if e[2] and cur_cols:
+                rg_tables.append(Table(cur_names, cur_cols).select(
+                    [n for n in rg_names if n in cur_names]))
+                cur_cols, cur_names = [], []
+            rg_names = e[1]
+            cur_cols.append(e[6])
+            cur_names.append(e[0])
+        if ok and cur_cols:
+            rg_tables.append(Table(cur_names, cur_cols).select(
+                [n for n in rg_names if n in cur_names]))
+        group, group_rgs = [], 0
+        return ok
+
+    try:
+        futs = [ex.submit(fetch, k) for k in range(len(items))]
         for k, fut in enumerate(futs):
+            fp, rg, cm, field, start, size, first, names = items[k]
+            if first:
+                if group_rgs >= _GROUP_ROW_GROUPS and not flush():
+                    return None
+                group_rgs += 1
             # backpressure: keep at most ~2x the slot depth of decoded
             # chunks in flight on the GPU (unbounded enqueue ran the
-            # allocator far ahead of execution on 600+-chunk shards)
-            if len(inflight) >= 2 * _NSLOTS:
-                inflight.pop(0).synchronize()
-            fp, rg, cm, field, start, size, first, names = items[k]
-            if first and cur_cols:
-                ordered = [n for n in cur_names]
-                rg_tables.append(Table(cur_names, cur_cols).select(
-                    [n for n in items[k - 1][7] if n in ordered]))
-                cur_cols, cur_names = [], []
+            # allocator far ahead of execution on 600+-chunk shards);
+            # the group being prepared counts, flushed work is waited for
+            while inflight and (sum(c for _, c in inflight) + len(group)
+                                >= 2 * _NSLOTS):
+                inflight.pop(0)[0].synchronize()
             i = fut.result()
             s = slots[i]
             view = s["np"][:size]
@@ -714,20 +825,26 @@ def _read_pieces_pipelined(my, columns, ctx) -> Optional[Table]:
                 None, cm, cm.physical_type,
                 max_def=1 if field.nullable else 0,
                 prefetched=(hdrs, dev, dict_raw, (fp, start, size)))
-            col = reader.decode_column(device, field)
-            done = torch.cuda.Event()
-            done.record()
-            inflight.append(done)
+            try:
+                prep = reader._prepare_batched(device)
+            except Exception:
+                prep = None
+            col = None
+            if prep is None:
+                # not eligible for the batched path: the per-chunk route
+                # now, so the chunk does not hold up its group
+                col = reader.decode_column(device, field)
+                done = torch.cuda.Event()
+                done.record()
+                inflight.append((done, 1))
             STATS["t_decode"] = STATS.get("t_decode", 0.0) + \
                 time.perf_counter() - t0
-            if col is None:
+            if prep is None and col is None:
                 return None
-            cur_cols.append(col)
-            cur_names.append(cm.path_in_schema)
-        if cur_cols:
-            last_names = items[-1][7]
-            rg_tables.append(Table(cur_names, cur_cols).select(
-                [n for n in last_names if n in cur_names]))
+            group.append([cm.path_in_schema, names, first, reader, field,
+                          prep, col])
+        if not flush():
+            return None
     finally:
         ex.shutdown(wait=True)
     if len(rg_tables) == 1:

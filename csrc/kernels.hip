@@ -1213,6 +1213,7 @@ torch::Tensor gemm_f32(torch::Tensor A, torch::Tensor B);  // gemm.hip
 // parquet.hip: page-parallel on-GPU parquet decode
 void pq_decompress(torch::Tensor src, torch::Tensor pages_blob,
                    int64_t n_pages, torch::Tensor scratch);
+void pq_decompress_multi(torch::Tensor pages_blob, int64_t n_pages);
 std::vector<torch::Tensor> pq_def_levels(torch::Tensor scratch,
                                          torch::Tensor pages_blob,
                                          int64_t n_pages, int64_t bitwidth,
@@ -1255,6 +1256,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("join_probe", &join_probe, "hash join probe");
   m.def("pq_decompress", &pq_decompress,
         "page-parallel snappy decompress (one wave/page)");
+  m.def("pq_decompress_multi", &pq_decompress_multi,
+        "snappy decompress over a table of absolute page addresses");
   m.def("pq_def_levels", &pq_def_levels,
         "definition levels -> validity mask + per-page valid counts");
   m.def("pq_expand_codes", &pq_expand_codes,

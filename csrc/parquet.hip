@@ -1,11 +1,16 @@
 // On-GPU Parquet decode kernels for gfx950 (MI355X): page-parallel snappy
 // decompression, definition-level -> validity-mask expansion, RLE/bit-packed
 // dictionary-code expansion, fixed-width value copy and BYTE_ARRAY (string)
-// assembly.  One 64-lane wavefront per page: lane 0 parses the sequential
-// byte stream (tags / run headers / varints) and broadcasts work items with
-// __shfl; all 64 lanes execute the copies/expansions cooperatively.  Pages
-// are the parallel axis — a shard decode runs thousands of pages at once,
-// which fills the 256 CUs.
+// assembly.  One 64-lane wavefront per page.  Snappy streams are parsed 64
+// candidate headers at a time out of an LDS window and executed one element
+// per lane (see pq_decompress_page); in the level / code / string kernels lane 0
+// parses run headers and varints and broadcasts work items with __shfl, and
+// all 64 lanes execute the expansions.  Pages are the parallel axis.  The
+// per-chunk entry points run one column chunk's pages per launch (420
+// pages of about 160 KB for a 2^23-row int64 chunk of the flagship shard);
+// pq_decompress_multi takes a table of absolute page addresses, so the
+// pipelined shard reader decompresses every column chunk of a group of row
+// groups in one launch (about 2100 pages per row group of that shard).
 //
 // Also hosts the C++ (host-side) page-header parser: a minimal Thrift
 // compact-protocol walk over the chunk buffer, returning a page table as
@@ -49,92 +54,319 @@ struct PageMeta {
 #define PQF_SNAPPY 2
 
 // ---------------------------------------------------------------------
-// snappy decompression, one wave per page
+// snappy decompression, one wave per page.
+//
+// The stream is walked 64 bytes at a time:
+//   window  - 1 KiB of the compressed stream sits in LDS (one wave per
+//             block), loaded with one coalesced 16-B load per lane;
+//   parse   - lane l decodes the element header that would start at byte
+//             l of the 64, then six rounds of pointer jumping over the
+//             lanes' "next header" links mark the lanes on the chain
+//             from byte 0: those hold the true elements.  A prefix sum
+//             of their lengths gives every element its output position;
+//   execute - every marked lane copies its own element.  A copy whose
+//             source lies in this batch's own output waits for a later
+//             round: a round runs each pending element whose source
+//             ends at or below the output position of the first pending
+//             element.
+// Elements longer than PQ_SHORT and overlapping copies (off < len) end a
+// batch and run wave-cooperatively, 16 B per lane where source and
+// destination do not overlap.  Between rounds the wave drains its own
+// vector-memory operations and fences at workgroup scope: the ordering
+// needed is between lanes of this one wave.
 // ---------------------------------------------------------------------
+
+#define PQ_WIN 1024   // window bytes: 16 per lane
+#define PQ_WIN_WORDS (PQ_WIN / 4 + 4)  // + zero words a peek may touch
+#define PQ_SHORT 32   // longest element a single lane copies
+
+struct PagePtr {  // page table entry of pq_decompress_multi
+  const uint8_t* src;  // compressed page body
+  uint8_t* dst;        // decompressed page
+  int32_t src_len;
+  int32_t dst_len;
+  int32_t flags;       // PQF_SNAPPY
+  int32_t pad;
+};
+
+DEV_INLINE int pq_uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
+
+template <class T>
+DEV_INLINE T* pq_uni_ptr(T* p) {
+  uint64_t v = (uint64_t)p;
+  uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+  uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32));
+  return (T*)(((uint64_t)hi << 32) | lo);
+}
+
+// stores of this wave become visible to later loads of this wave
+DEV_INLINE void pq_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+// Load stream bytes [pos, pos + PQ_WIN) into win, pos = ip rounded down
+// to a 16-B address; returns pos (may be < 0).  Bytes outside
+// [0, src_len) are never read: they are 0.  The block is one wave.
+DEV_INLINE int pq_window_load(uint32_t* win, const uint8_t* __restrict__ in,
+                              int ip, int src_len, int lane) {
+  int pos = ip - (int)((uintptr_t)(in + ip) & 15);
+  int c = pos + lane * 16;
+  const uint8_t* g = in + c;
+  uint4 v;
+  if (c >= 0 && c + 16 <= src_len) {
+    v = *(const uint4*)g;
+  } else {
+    uint32_t w[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int b = 0; b < 16; ++b) {
+      int q = c + b;
+      if (q >= 0 && q < src_len) w[b >> 2] |= (uint32_t)g[b] << (8 * (b & 3));
+    }
+    v = make_uint4(w[0], w[1], w[2], w[3]);
+  }
+  __syncthreads();  // reads of the previous window are done
+  *(uint4*)(win + lane * 4) = v;
+  if (lane < 4) win[PQ_WIN / 4 + lane] = 0;
+  __syncthreads();
+  return pos;
+}
+
+// 8 bytes at window offset rel, 0 <= rel < PQ_WIN
+DEV_INLINE uint64_t pq_window_peek(const uint32_t* win, int rel) {
+  const uint32_t* q = win + (rel >> 2);
+  uint64_t v = (uint64_t)q[0] | ((uint64_t)q[1] << 32);
+  return v >> ((rel & 3) * 8);  // 5 bytes or more are valid
+}
+
+DEV_INLINE int pq_lane_get(int v, int src_lane) {  // per-lane source
+  return __builtin_amdgcn_ds_bpermute(src_lane << 2, v);
+}
+
+// one lane copies len <= PQ_SHORT bytes; [s, s+len) and [d, d+len) are
+// disjoint, nothing outside them is touched
+DEV_INLINE void pq_lane_copy(uint8_t* d, const uint8_t* s, int len) {
+  uint64_t v[PQ_SHORT / 8];
+  uint32_t t4 = 0;
+  uint16_t t2 = 0;
+  uint8_t t1 = 0;
+  int nq = len >> 3;
+#pragma unroll
+  for (int q = 0; q < PQ_SHORT / 8; ++q)
+    if (q < nq) __builtin_memcpy(&v[q], s + 8 * q, 8);
+  int r = nq * 8;
+  if (len & 4) { __builtin_memcpy(&t4, s + r, 4); r += 4; }
+  if (len & 2) { __builtin_memcpy(&t2, s + r, 2); r += 2; }
+  if (len & 1) t1 = s[r];
+#pragma unroll
+  for (int q = 0; q < PQ_SHORT / 8; ++q)
+    if (q < nq) __builtin_memcpy(d + 8 * q, &v[q], 8);
+  r = nq * 8;
+  if (len & 4) { __builtin_memcpy(d + r, &t4, 4); r += 4; }
+  if (len & 2) { __builtin_memcpy(d + r, &t2, 2); r += 2; }
+  if (len & 1) d[r] = t1;
+}
+
+// the wave copies len bytes, disjoint ranges: byte head up to a 16-B
+// destination boundary, 16 B per lane, byte tail
+DEV_INLINE void pq_wave_copy(uint8_t* d, const uint8_t* s, int len, int lane) {
+  int head = (int)((0 - (uintptr_t)d) & 15);
+  if (head > len) head = len;
+  if (lane < head) d[lane] = s[lane];
+  int body = (len - head) & ~15;
+  uint8_t* db = d + head;
+  const uint8_t* sb = s + head;
+  int i = lane * 16;
+  for (; i + 3 * WAVE * 16 < body; i += 4 * WAVE * 16) {  // 4 loads in flight
+    uint4 v0, v1, v2, v3;
+    __builtin_memcpy(&v0, sb + i, 16);
+    __builtin_memcpy(&v1, sb + i + WAVE * 16, 16);
+    __builtin_memcpy(&v2, sb + i + 2 * WAVE * 16, 16);
+    __builtin_memcpy(&v3, sb + i + 3 * WAVE * 16, 16);
+    *(uint4*)(db + i) = v0;
+    *(uint4*)(db + i + WAVE * 16) = v1;
+    *(uint4*)(db + i + 2 * WAVE * 16) = v2;
+    *(uint4*)(db + i + 3 * WAVE * 16) = v3;
+  }
+  for (; i < body; i += WAVE * 16) {
+    uint4 v;
+    __builtin_memcpy(&v, sb + i, 16);
+    *(uint4*)(db + i) = v;
+  }
+  int t = head + body + lane;
+  if (t < len) d[t] = s[t];
+}
+
+// All arguments but lane are wave-uniform; win is this wave's window.
+DEV_INLINE void pq_decompress_page(const uint8_t* __restrict__ in,
+                                   uint8_t* out, int src_len, int dst_len,
+                                   int flags, int lane, uint32_t* win) {
+  if (!(flags & PQF_SNAPPY)) {  // uncompressed page: copy into scratch
+    pq_wave_copy(out, in, dst_len, lane);
+    return;
+  }
+  if (src_len <= 0) return;
+  int wpos = pq_window_load(win, in, 0, src_len, lane);
+  int ip = 0, opos = 0;
+  {  // skip the uncompressed-length varint preamble (at most 5 bytes)
+    bool more = true;
+    for (int i = 0; i < 5 && more; ++i) {
+      if (ip >= src_len) return;
+      more = pq_window_peek(win, ip - wpos) & 0x80;
+      ip++;
+    }
+    if (more) return;  // corrupt
+  }
+  while (ip < src_len && opos < dst_len) {
+    // 64 candidate headers + 5 header bytes stay inside the window
+    if (ip - wpos > PQ_WIN - WAVE - 5)
+      wpos = pq_window_load(win, in, ip, src_len, lane);
+    // ---- parse: this lane's candidate header at stream position p
+    int p = ip + lane;
+    uint64_t h = pq_window_peek(win, p - wpos);
+    int tag = (int)(h & 0xFF);
+    int k = tag & 3;
+    int len = (tag >> 2) + 1, hl, off = 0;
+    bool bad = false;
+    if (k == 0) {  // literal
+      hl = 1;
+      if (len > 60) {
+        int nb = len - 60;
+        uint32_t raw = (uint32_t)(h >> 8);
+        if (nb < 4) raw &= (1u << (8 * nb)) - 1;
+        bad = raw >= 0x7FFFFFFFu;
+        len = bad ? 1 : (int)raw + 1;
+        hl = 1 + nb;
+      }
+    } else if (k == 1) {
+      len = ((tag >> 2) & 7) + 4;
+      off = ((tag >> 5) << 8) | (int)((h >> 8) & 0xFF);
+      hl = 2;
+    } else if (k == 2) {
+      off = (int)((h >> 8) & 0xFFFF);
+      hl = 3;
+    } else {
+      uint32_t o = (uint32_t)(h >> 8);
+      bad = o > 0x7FFFFFFFu;
+      off = (int)(o & 0x7FFFFFFFu);
+      hl = 5;
+    }
+    // corrupt input stops the page: header or literal past src_len, ...
+    bool live = p < src_len;
+    bad = bad || hl > src_len - p;
+    if (k == 0) bad = bad || len > src_len - p - hl;
+    else bad = bad || off <= 0;
+    bool coop = len > PQ_SHORT || (k != 0 && off < len);
+    bool stop = bad || coop;
+    // stream bytes to the next header; meaningful when !stop: <= 37
+    int adv = hl + (k == 0 && !stop ? len : 0);
+    // ---- the lanes on the chain from byte 0 hold the real elements
+    uint32_t mlo = live && lane < 32 ? 1u << lane : 0;
+    uint32_t mhi = live && lane >= 32 ? 1u << (lane - 32) : 0;
+    int jump = (!live || stop || lane + adv > WAVE - 1) ? WAVE : lane + adv;
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+      int sl = jump & (WAVE - 1);
+      uint32_t tlo = (uint32_t)pq_lane_get((int)mlo, sl);
+      uint32_t thi = (uint32_t)pq_lane_get((int)mhi, sl);
+      int tj = pq_lane_get(jump, sl);
+      if (jump < WAVE) {
+        mlo |= tlo;
+        mhi |= thi;
+        jump = tj;
+      }
+    }
+    uint64_t chain = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)mhi) << 32) |
+                     (uint32_t)__builtin_amdgcn_readfirstlane((int)mlo);
+    bool on = (chain >> lane) & 1;
+    // ---- output positions: exclusive prefix sum of the element lengths
+    // (a long element is last on the chain, so the sum cannot overflow)
+    int mylen = on ? len : 0;
+    int incl = mylen;
+#pragma unroll
+    for (int d = 1; d < WAVE; d <<= 1) {
+      int t = __shfl_up(incl, d);
+      if (lane >= d) incl += t;
+    }
+    int m_o = opos + (incl - mylen);
+    // ... output past dst_len, copy from before the start of the output
+    bad = bad || len > dst_len - m_o || (k != 0 && off > m_o);
+    stop = bad || coop;
+    uint64_t stops = __ballot(on && stop);
+    int s = stops ? __builtin_ctzll(stops) : WAVE;  // first stopping element
+    uint64_t batch = s < WAVE ? chain & ((1ull << s) - 1) : chain;
+    // ---- execute the short elements before s
+    bool pend = (batch >> lane) & 1;
+    int m_src = p + hl;
+    while (true) {
+      uint64_t pm = __ballot(pend);
+      if (!pm) break;
+      // everything below the first pending element's output is complete
+      int done_to = __builtin_amdgcn_readlane(m_o, __builtin_ctzll(pm));
+      if (pend && (k == 0 || m_o - off + len <= done_to)) {
+        const uint8_t* sp = k ? out + (m_o - off) : in + m_src;
+        pq_lane_copy(out + m_o, sp, len);
+        pend = false;
+      }
+      pq_wave_sync();
+    }
+    if (s == WAVE) {  // the whole chain ran: go on behind its last element
+      int last = 63 - __builtin_clzll(chain);
+      opos += __builtin_amdgcn_readlane(incl, last);
+      ip += __builtin_amdgcn_readlane(lane + adv, last);
+      continue;
+    }
+    if (__builtin_amdgcn_readlane((int)bad, s)) return;  // corrupt
+    // ---- element s runs wave-cooperatively
+    opos = __builtin_amdgcn_readlane(m_o, s);
+    int big_len = __builtin_amdgcn_readlane(len, s);
+    int big_off = __builtin_amdgcn_readlane(off, s);
+    int big_k = __builtin_amdgcn_readlane(k, s);
+    int big_src = ip + s + __builtin_amdgcn_readlane(hl, s);
+    uint8_t* d = out + opos;
+    if (big_k == 0) {
+      pq_wave_copy(d, in + big_src, big_len, lane);
+    } else if (big_off >= big_len) {
+      pq_wave_copy(d, d - big_off, big_len, lane);
+    } else {  // overlapping copy = pattern replication
+      const uint8_t* sp = d - big_off;
+      for (int i = lane; i < big_len; i += WAVE) d[i] = sp[i % big_off];
+    }
+    pq_wave_sync();
+    opos += big_len;
+    ip = big_src + (big_k == 0 ? big_len : 0);
+  }
+}
 
 __global__ void pq_decompress_kernel(const uint8_t* __restrict__ src,
                                      const PageMeta* __restrict__ pages,
-                                     int n_pages, uint8_t* __restrict__ dst) {
-  int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
+                                     int n_pages, uint8_t* dst) {
+  int wave = pq_uni((int)((blockIdx.x * blockDim.x + threadIdx.x) / WAVE));
   int lane = threadIdx.x % WAVE;
-  int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) / WAVE;
-  for (int64_t p = wave; p < n_pages; p += n_waves) {
-    PageMeta pm = pages[p];
-    const uint8_t* in = src + pm.src_off;
-    uint8_t* out = dst + pm.dst_off;
-    if (!(pm.flags & PQF_SNAPPY)) {
-      // uncompressed page: cooperative copy into scratch
-      for (int64_t i = lane; i < pm.dst_len; i += WAVE) out[i] = in[i];
-      continue;
-    }
-    int64_t ip = 0, opos = 0;
-    int64_t src_len = pm.src_len, dst_len = pm.dst_len;
-    if (lane == 0) {  // skip the uncompressed-length varint preamble
-      while (in[ip] & 0x80) ip++;
-      ip++;
-    }
-    ip = __shfl(ip, 0);
-    while (ip < src_len && opos < dst_len) {
-      int64_t v0 = 0, v1 = 0;
-      if (lane == 0) {
-        uint8_t tag = in[ip];
-        int k = tag & 3;
-        if (k == 0) {  // literal
-          int64_t len = (tag >> 2) + 1;
-          int hl = 1;
-          if (len > 60) {
-            int nb = (int)(len - 60);
-            len = 0;
-            for (int i = 0; i < nb; ++i)
-              len |= (int64_t)in[ip + 1 + i] << (8 * i);
-            len += 1;
-            hl = 1 + nb;
-          }
-          v0 = (len << 8);          // kind 0 in low byte
-          v1 = ip + hl;             // literal source offset
-          ip += hl + len;
-        } else {
-          int64_t len, off;
-          int hl;
-          if (k == 1) {
-            len = ((tag >> 2) & 7) + 4;
-            off = ((int64_t)(tag >> 5) << 8) | in[ip + 1];
-            hl = 2;
-          } else if (k == 2) {
-            len = (tag >> 2) + 1;
-            off = (int64_t)in[ip + 1] | ((int64_t)in[ip + 2] << 8);
-            hl = 3;
-          } else {
-            len = (tag >> 2) + 1;
-            off = (int64_t)in[ip + 1] | ((int64_t)in[ip + 2] << 8) |
-                  ((int64_t)in[ip + 3] << 16) | ((int64_t)in[ip + 4] << 24);
-            hl = 5;
-          }
-          v0 = (len << 8) | 1;      // kind 1: copy
-          v1 = off;
-          ip += hl;
-        }
-      }
-      v0 = __shfl(v0, 0);
-      v1 = __shfl(v1, 0);
-      ip = __shfl(ip, 0);
-      int64_t len = v0 >> 8;
-      if (len <= 0 || opos + len > dst_len) break;  // corrupt: stop
-      if ((v0 & 0xFF) == 0) {
-        const uint8_t* s = in + v1;
-        for (int64_t i = lane; i < len; i += WAVE) out[opos + i] = s[i];
-      } else {
-        int64_t off = v1;
-        if (off <= 0 || off > opos) break;  // corrupt
-        const uint8_t* s = out + opos - off;
-        if (off >= len) {
-          for (int64_t i = lane; i < len; i += WAVE) out[opos + i] = s[i];
-        } else {  // overlapping copy = pattern replication
-          for (int64_t i = lane; i < len; i += WAVE) out[opos + i] = s[i % off];
-        }
-      }
-      opos += len;
-    }
+  int n_waves = (int)((gridDim.x * blockDim.x) / WAVE);
+  __shared__ uint32_t win[PQ_WIN_WORDS];  // blocks are one wave
+  for (int p = wave; p < n_pages; p += n_waves) {
+    const PageMeta* pm = pages + p;
+    pq_decompress_page(pq_uni_ptr(src + pm->src_off),
+                       pq_uni_ptr(dst + pm->dst_off), pq_uni(pm->src_len),
+                       pq_uni(pm->dst_len), pq_uni(pm->flags), lane, win);
+  }
+}
+
+// same body over a table of absolute addresses: one launch covers pages
+// of many column chunks, each with its own source and scratch tensor
+__global__ void pq_decompress_multi_kernel(const PagePtr* __restrict__ pages,
+                                           int n_pages) {
+  int wave = pq_uni((int)((blockIdx.x * blockDim.x + threadIdx.x) / WAVE));
+  int lane = threadIdx.x % WAVE;
+  int n_waves = (int)((gridDim.x * blockDim.x) / WAVE);
+  __shared__ uint32_t win[PQ_WIN_WORDS];  // blocks are one wave
+  for (int p = wave; p < n_pages; p += n_waves) {
+    const PagePtr* pm = pages + p;
+    pq_decompress_page(pq_uni_ptr(pm->src), pq_uni_ptr(pm->dst),
+                       pq_uni(pm->src_len), pq_uni(pm->dst_len),
+                       pq_uni(pm->flags), lane, win);
   }
 }
 
@@ -411,15 +643,34 @@ static int pq_grid_waves(int64_t n_pages, int block) {
   return (int)b;
 }
 
+// one wave per page, one wave per block: the pages of a launch differ a
+// lot in cost, and single-wave blocks let the dispatcher spread them
+static int pq_grid_pages(int64_t n_pages) {
+  return (int)std::min<int64_t>(std::max<int64_t>(n_pages, 1), 1 << 20);
+}
+
 void pq_decompress(torch::Tensor src, torch::Tensor pages_blob,
                    int64_t n_pages, torch::Tensor scratch) {
   if (!n_pages) return;
-  int block = 256;
-  hipLaunchKernelGGL(pq_decompress_kernel,
-                     dim3(pq_grid_waves(n_pages, block)), dim3(block), 0,
-                     pq_stream(), (const uint8_t*)src.data_ptr(),
+  hipLaunchKernelGGL(pq_decompress_kernel, dim3(pq_grid_pages(n_pages)),
+                     dim3(WAVE), 0, pq_stream(),
+                     (const uint8_t*)src.data_ptr(),
                      (const PageMeta*)pages_blob.data_ptr(), (int)n_pages,
                      (uint8_t*)scratch.data_ptr());
+  CHECK_HIP_PQ(hipGetLastError());
+}
+
+// pages_blob: device bytes of n_pages PagePtr entries (absolute device
+// addresses).  The caller keeps the tensors they point into alive.
+void pq_decompress_multi(torch::Tensor pages_blob, int64_t n_pages) {
+  if (!n_pages) return;
+  TORCH_CHECK(pages_blob.is_contiguous() &&
+                  pages_blob.numel() * pages_blob.element_size() >=
+                      n_pages * (int64_t)sizeof(PagePtr),
+              "pq_decompress_multi: page table too small");
+  hipLaunchKernelGGL(pq_decompress_multi_kernel,
+                     dim3(pq_grid_pages(n_pages)), dim3(WAVE), 0, pq_stream(),
+                     (const PagePtr*)pages_blob.data_ptr(), (int)n_pages);
   CHECK_HIP_PQ(hipGetLastError());
 }
 
