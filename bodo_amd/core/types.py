@@ -123,7 +123,10 @@ _TORCH_STORAGE = {
     TypeKind.INT32: torch.int32,
     TypeKind.INT64: torch.int64,
     TypeKind.UINT8: torch.uint8,
-    TypeKind.UINT16: torch.int16,  # stored as bit-identical signed
+    # unsigned 16/32/64-bit columns may sit in the bit-identical signed dtype
+    # (from_numpy) or in torch's unsigned one (from_arrow); kernels and
+    # hashes read the bits as unsigned either way
+    TypeKind.UINT16: torch.int16,
     TypeKind.UINT32: torch.int32,
     TypeKind.UINT64: torch.int64,
     TypeKind.FLOAT32: torch.float32,

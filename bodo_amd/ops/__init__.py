@@ -339,6 +339,13 @@ def _col_hash_cpu(c: Column, seed: int) -> np.ndarray:
         bits[f == 0.0] = 0  # -0.0 == 0.0
         bits[np.isnan(f)] = np.uint64(0x7FF8000000000000)
         h = _mix64_np(bits)
+    elif k in (TypeKind.UINT16, TypeKind.UINT32):
+        # unsigned columns hash their zero-extended value whether the storage
+        # tensor is the unsigned torch dtype or its bit-identical signed one
+        # (matches csrc hash_value)
+        raw = c.data.numpy()
+        h = _mix64_np(raw.view(f"uint{raw.dtype.itemsize * 8}")
+                      .astype(np.uint64))
     else:
         h = _mix64_np(c.data.numpy().astype(np.int64).view(np.uint64))
     if c.mask is not None:

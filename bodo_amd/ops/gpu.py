@@ -45,17 +45,19 @@ _DICT_HASH_CACHE: dict = {}
 
 def _dict_hash_lut(col: Column) -> torch.Tensor:
     key = (id(col.dictionary), str(col.device))
-    lut = _DICT_HASH_CACHE.get(key)
+    # the entry keeps its dictionary alive, so the id cannot be reused by
+    # another dictionary while the entry exists
+    lut = _DICT_HASH_CACHE.get(key, (None, None))[0]
     if lut is None:
         vals = col.dictionary.to_pylist()
         arr = np.array(
             [_fnv_bytes(v.encode() if v is not None else b"") for v in vals],
             dtype=np.uint64)
         lut = torch.from_numpy(arr.view(np.int64)).to(col.device)
-        _DICT_HASH_CACHE[key] = lut
+        _DICT_HASH_CACHE[key] = (lut, col.dictionary)
         if len(_DICT_HASH_CACHE) > 256:
             _DICT_HASH_CACHE.clear()
-            _DICT_HASH_CACHE[key] = lut
+            _DICT_HASH_CACHE[key] = (lut, col.dictionary)
     return lut
 
 
@@ -145,7 +147,9 @@ _AGG_OP = {
     "prod_f64": 10,
 }
 
-_F64_MAX = float(np.finfo(np.float64).max)
+# float min/max accumulators start at the identity of the op, so a group
+# whose valid values are all +inf (min) or all -inf (max) keeps them
+_F64_INF = float("inf")
 _I64_MAX = int(np.iinfo(np.int64).max)
 _I64_MIN = int(np.iinfo(np.int64).min)
 
@@ -307,7 +311,7 @@ def _run_fused(batch, row_gid, ngroups, results):
         else:  # min / max
             if is_float:
                 ops_.append(_AGG_OP[f"{func}_f64"])
-                init_fs.append(_F64_MAX if func == "min" else -_F64_MAX)
+                init_fs.append(_F64_INF if func == "min" else -_F64_INF)
                 init_is.append(0)
                 wants.append(1)
                 posts.append(("minmax_f64", None))
@@ -416,7 +420,7 @@ def _agg_one(col: Optional[Column], row_gid: torch.Tensor, ngroups: int,
         return Column(bt.int64, acc)
     if func in ("min", "max"):
         if is_float:
-            init = _F64_MAX if func == "min" else -_F64_MAX
+            init = _F64_INF if func == "min" else -_F64_INF
             acc, cnt = upd(f"{func}_f64", init_f=init, want_count=True)
             empty = cnt == 0
             acc = torch.where(empty, torch.full_like(acc, float("nan")), acc)
@@ -597,6 +601,49 @@ def _groupby_pairs(gid_col: Column, col: Column):
 # join
 # ----------------------------------------------------------------------
 
+def _unify_dict_keys(bkeys: Sequence[Column],
+                     pkeys: Sequence[Column]) -> List[Column]:
+    """The probe kernels compare dictionary-encoded keys by code, so a
+    DICT/DICT key pair must index one dictionary: extend the probe side's
+    dictionary with the build side's unseen values and remap the build
+    codes into it (hashes are by value and stay as they were).  The probe
+    side keeps its codes, so only one column is rewritten; concat_columns
+    and the shuffle's _remap_dict_codes merge dictionaries too, but remap
+    every input.
+
+    A DICT key against a STRING key is not handled here or in the kernels
+    (rows_eq2 switches on the probe column's type only); callers must bring
+    both sides to one encoding first."""
+    import pyarrow as pa
+
+    out = list(bkeys)
+    for i, (b, p) in enumerate(zip(bkeys, pkeys)):
+        if b.dtype.kind != TypeKind.DICT or p.dtype.kind != TypeKind.DICT:
+            continue
+        if b.dictionary is p.dictionary or b.dictionary.equals(p.dictionary):
+            continue
+        merged = p.dictionary.to_pylist()
+        code_of = {}
+        for j, v in enumerate(merged):
+            code_of.setdefault(v, j)
+        remap = np.empty(len(b.dictionary), dtype=np.int32)
+        for j, v in enumerate(b.dictionary.to_pylist()):
+            c = code_of.get(v)
+            if c is None:
+                c = code_of[v] = len(merged)
+                merged.append(v)
+            remap[j] = c
+        codes = b.data
+        if len(remap):
+            # the code under a null row is unspecified: clamp before indexing
+            idx = b.data.long().clamp(0, len(remap) - 1)
+            codes = torch.from_numpy(remap).to(b.device)[idx]
+        out[i] = Column(bt.dictionary, codes, b.mask,
+                        dictionary=pa.array(merged, type=pa.large_string()),
+                        length=len(b))
+    return out
+
+
 def join_local(left: Table, right: Table, left_on: Sequence[str],
                right_on: Sequence[str], how: str, suffixes=("_x", "_y")) -> Table:
     from . import take_table
@@ -617,6 +664,7 @@ def join_local(left: Table, right: Table, left_on: Sequence[str],
     build, probe = right, left
     bkeys = [build.column(k) for k in right_on]
     pkeys = [probe.column(k) for k in left_on]
+    bkeys = _unify_dict_keys(bkeys, pkeys)
     n_build, n_probe = len(build), len(probe)
     bh = hash_columns(bkeys) if n_build else torch.zeros(0, dtype=torch.int64, device=build.device)
     ph = hash_columns(pkeys) if n_probe else torch.zeros(0, dtype=torch.int64, device=build.device)

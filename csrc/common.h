@@ -63,10 +63,10 @@ DEV_INLINE uint64_t hash_value(const ColumnDesc& c, int64_t i) {
     case BT_INT8: return mix64((uint64_t)(int64_t)((const int8_t*)c.data)[i]);
     case BT_UINT8: return mix64((uint64_t)(int64_t)((const uint8_t*)c.data)[i]);
     case BT_INT16: return mix64((uint64_t)(int64_t)((const int16_t*)c.data)[i]);
-    case BT_UINT16: return mix64((uint64_t)(int64_t)((const int16_t*)c.data)[i]);
+    case BT_UINT16: return mix64((uint64_t)((const uint16_t*)c.data)[i]);
     case BT_INT32: case BT_DATE32:
       return mix64((uint64_t)(int64_t)((const int32_t*)c.data)[i]);
-    case BT_UINT32: return mix64((uint64_t)(int64_t)((const int32_t*)c.data)[i]);
+    case BT_UINT32: return mix64((uint64_t)((const uint32_t*)c.data)[i]);
     case BT_INT64: case BT_TIMESTAMP_NS: case BT_UINT64: case BT_DECIMAL128:
       // DECIMAL128 is stored as scaled int64 (exact for p <= 18)
       return mix64((uint64_t)((const int64_t*)c.data)[i]);

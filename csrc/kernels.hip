@@ -311,6 +311,44 @@ __global__ void gb_insert_kernel(const ColumnDesc* __restrict__ cols, int ncols,
   }
 }
 
+// Host-side sizing shared by both group builds.  The open-addressing insert
+// kernels probe until they find their key or an empty slot, so the host must
+// never launch an insert that could fill the table.
+#define GB_CHUNK_ROWS (int64_t(1) << 27)
+#define GB_MAX_INITIAL_CAP (int64_t(1) << 26)
+#define GB_PACKED_MAX_INITIAL_CAP (int64_t(1) << 25)
+
+static void check_build_limits(int64_t chunk_rows, int64_t max_initial_cap) {
+  TORCH_CHECK(chunk_rows >= 1, "chunk_rows must be positive");
+  TORCH_CHECK(max_initial_cap >= 16 &&
+                  (max_initial_cap & (max_initial_cap - 1)) == 0,
+              "max_initial_cap must be a power of two >= 16");
+}
+
+// Rows per insert launch.  With cap >= 2n the whole input fits below half
+// load and chunk_rows is used as is.  Otherwise each launch is clamped to
+// cap/2 - 1 rows and the load factor is checked after it: a launch starts
+// with occupied <= cap/2 (else the check before it would have grown the
+// table) and adds at most cap/2 - 1 entries, so occupied <= cap - 1.
+static int64_t insert_step(int64_t chunk_rows, int64_t cap, int64_t n) {
+  if (cap >= 2 * n) return chunk_rows;
+  return std::min(chunk_rows, cap / 2 - 1);
+}
+
+// Capacity after the load factor crossed 1/2 with `occupied` slots in use:
+// grow 8x (more if the groups seen so far suggest it), never past the
+// smallest power of two >= 2n, at which no further check is needed.
+static int64_t grown_cap(int64_t cap, int64_t occupied, int64_t n) {
+  int64_t want = cap * 8;
+  while (want < 2 * std::min(n, occupied * 8)) want <<= 1;
+  if (want > 2 * n) {
+    int64_t c2 = 16;
+    while (c2 < 2 * n) c2 <<= 1;
+    want = c2;
+  }
+  return want;
+}
+
 // two-pass group-id assignment: pass 1 counts occupied slots per block
 // (no atomics), host cumsums 2048 values, pass 2 assigns gids via an LDS
 // counter (one global atomic total: zero).  Replaces a single-global-counter
@@ -348,7 +386,9 @@ __global__ void gb_insert_packed_kernel(const int64_t* __restrict__ keys,
                                         uint32_t* __restrict__ slot_rows,
                                         uint64_t cap_mask,
                                         uint32_t* __restrict__ row_slot,
-                                        int64_t n) {
+                                        int64_t n, int64_t row0) {
+  // rows [row0, row0+n) of the table; keys/row_slot pre-offset by caller,
+  // slot_rows stores the global row+1
   GRID_STRIDE_LOOP(i, n) {
     unsigned long long key = (unsigned long long)keys[i];
     uint64_t s = mix64(key) & cap_mask;
@@ -361,7 +401,7 @@ __global__ void gb_insert_packed_kernel(const int64_t* __restrict__ keys,
       if (old == PACKED_EMPTY) {
         old = atomicCAS(&slot_keys[s], PACKED_EMPTY, key);
         if (old == PACKED_EMPTY) {
-          slot_rows[s] = (uint32_t)(i + 1);
+          slot_rows[s] = (uint32_t)(row0 + i + 1);
           row_slot[i] = (uint32_t)s;
           break;
         }
@@ -414,41 +454,40 @@ __global__ void gb_count_packed_kernel(
   if (threadIdx.x == 0) block_counts[blockIdx.x] = red[0];
 }
 
-std::vector<torch::Tensor> groupby_build_packed(torch::Tensor keys) {
+std::vector<torch::Tensor> groupby_build_packed(torch::Tensor keys,
+                                                int64_t chunk_rows,
+                                                int64_t max_initial_cap) {
   auto dev = keys.device();
   int64_t n = keys.numel();
+  check_build_limits(chunk_rows, max_initial_cap);
   int block = 256;
   // 2^25 slots x 8 B = 256 MB: Infinity-Cache resident; grow on pressure
   int64_t cap = 16;
   while (cap < 2 * n) cap <<= 1;
-  if (cap > (1 << 25)) cap = 1 << 25;
+  if (cap > max_initial_cap) cap = max_initial_cap;
   auto row_slot = torch::empty({n}, torch::dtype(torch::kInt32).device(dev));
   torch::Tensor slot_keys, slot_rows;
-  const int64_t chunk_rows = 1 << 27;
   while (true) {
     slot_keys = torch::full({cap}, -1, torch::dtype(torch::kInt64).device(dev));
     slot_rows = torch::empty({cap}, torch::dtype(torch::kInt32).device(dev));
     bool grown = false;
-    for (int64_t start = 0; start < n; start += chunk_rows) {
-      int64_t cnt = std::min(chunk_rows, n - start);
+    // Invariant (see insert_step): while cap < 2n a launch adds at most
+    // cap/2 - 1 keys and starts with occupied <= cap/2, so occupied < cap
+    // always holds and every probe finds a free slot or its key.
+    const int64_t step = insert_step(chunk_rows, cap, n);
+    for (int64_t start = 0; start < n; start += step) {
+      int64_t cnt = std::min(step, n - start);
       hipLaunchKernelGGL(gb_insert_packed_kernel, dim3(grid_for(cnt, block)),
                          dim3(block), 0, cur_stream(),
                          (const int64_t*)keys.data_ptr() + start,
                          (unsigned long long*)slot_keys.data_ptr(),
                          (uint32_t*)slot_rows.data_ptr(), (uint64_t)(cap - 1),
-                         (uint32_t*)row_slot.data_ptr() + start, cnt);
+                         (uint32_t*)row_slot.data_ptr() + start, cnt, start);
       CHECK_HIP(hipGetLastError());
       if (start + cnt < n && cap < 2 * n) {
         int64_t occupied = (slot_keys != -1).sum().item<int64_t>();
         if (occupied * 2 > cap) {
-          int64_t want = cap * 8;
-          while (want < 2 * std::min(n, occupied * 8)) want <<= 1;
-          if (want > 2 * n) {
-            int64_t c2 = 16;
-            while (c2 < 2 * n) c2 <<= 1;
-            want = c2;
-          }
-          cap = want;
+          cap = grown_cap(cap, occupied, n);
           grown = true;
           break;
         }
@@ -521,25 +560,34 @@ std::vector<torch::Tensor> groupby_build(
     std::vector<c10::optional<torch::Tensor>> masks,
     std::vector<c10::optional<torch::Tensor>> offsets,
     std::vector<c10::optional<torch::Tensor>> auxs,
-    std::vector<int64_t> dtypes, int64_t n, torch::Tensor hashes) {
+    std::vector<int64_t> dtypes, int64_t n, torch::Tensor hashes,
+    int64_t chunk_rows, int64_t max_initial_cap) {
   auto dev = datas[0].device();
   auto ds = build_descset(datas, masks, offsets, auxs, dtypes, n);
+  check_build_limits(chunk_rows, max_initial_cap);
   // Start with an Infinity-Cache-resident table (2^26 slots = 256 MB):
   // the random atomicCAS probes then hit L3 instead of HBM (guide §2).
   // Insert in chunks, checking the load factor between chunks; grow 8x and
   // re-insert when it crosses 1/2 (few groupbys exceed 32M groups/rank).
+  // While the table is smaller than 2n slots a chunk is at most cap/2 - 1
+  // rows (insert_step), each followed by a device sync and a count of the
+  // table: n above 2^25 rows takes several launches where chunk_rows alone
+  // would give one.
   int64_t cap = 16;
   while (cap < 2 * n) cap <<= 1;
-  if (cap > (1 << 26)) cap = 1 << 26;
+  if (cap > max_initial_cap) cap = max_initial_cap;
   int block = 256;
   auto row_slot = torch::empty({n}, torch::dtype(torch::kInt32).device(dev));
   torch::Tensor slots;
-  const int64_t chunk_rows = 1 << 27;
   while (true) {
     slots = torch::zeros({cap}, torch::dtype(torch::kInt32).device(dev));
     bool grown = false;
-    for (int64_t start = 0; start < n; start += chunk_rows) {
-      int64_t cnt = std::min(chunk_rows, n - start);
+    // Invariant (see insert_step): while cap < 2n a launch adds at most
+    // cap/2 - 1 groups and starts with occupied <= cap/2, so occupied < cap
+    // always holds and every probe finds a free slot or its group.
+    const int64_t step = insert_step(chunk_rows, cap, n);
+    for (int64_t start = 0; start < n; start += step) {
+      int64_t cnt = std::min(step, n - start);
       hipLaunchKernelGGL(gb_insert_kernel, dim3(grid_for(cnt, block)),
                          dim3(block), 0, cur_stream(), ds.ptr(),
                          (int)datas.size(),
@@ -549,16 +597,9 @@ std::vector<torch::Tensor> groupby_build(
                          (const uint64_t*)hashes.data_ptr());
       CHECK_HIP(hipGetLastError());
       if (start + cnt < n && cap < 2 * n) {
-        int64_t occupied = (slots != 0).sum().item<int64_t>();
+        int64_t occupied = torch::count_nonzero(slots).item<int64_t>();
         if (occupied * 2 > cap) {
-          int64_t want = cap * 8;
-          while (want < 2 * std::min(n, occupied * 8)) want <<= 1;
-          if (want > 2 * n) {
-            int64_t c2 = 16;
-            while (c2 < 2 * n) c2 <<= 1;
-            want = c2;
-          }
-          cap = want;
+          cap = grown_cap(cap, occupied, n);
           grown = true;
           break;  // rebuild from scratch at the bigger capacity
         }
@@ -625,9 +666,11 @@ __global__ void agg_update_kernel(const ColumnDesc col,
       switch (col.dtype) {
         case BT_INT8: iv = ((const int8_t*)col.data)[i]; dv = (double)iv; break;
         case BT_UINT8: case BT_BOOL: iv = ((const uint8_t*)col.data)[i]; dv = (double)iv; break;
-        case BT_INT16: case BT_UINT16: iv = ((const int16_t*)col.data)[i]; dv = (double)iv; break;
-        case BT_INT32: case BT_UINT32: case BT_DATE32: case BT_DICT:
+        case BT_INT16: iv = ((const int16_t*)col.data)[i]; dv = (double)iv; break;
+        case BT_UINT16: iv = ((const uint16_t*)col.data)[i]; dv = (double)iv; break;
+        case BT_INT32: case BT_DATE32: case BT_DICT:
           iv = ((const int32_t*)col.data)[i]; dv = (double)iv; break;
+        case BT_UINT32: iv = ((const uint32_t*)col.data)[i]; dv = (double)iv; break;
         case BT_INT64: case BT_UINT64: case BT_TIMESTAMP_NS:
           iv = ((const int64_t*)col.data)[i]; dv = (double)iv; break;
         case BT_FLOAT32: {
@@ -704,9 +747,11 @@ __global__ void agg_update_lds_kernel(const ColumnDesc col,
       switch (col.dtype) {
         case BT_INT8: iv = ((const int8_t*)col.data)[i]; dv = (double)iv; break;
         case BT_UINT8: case BT_BOOL: iv = ((const uint8_t*)col.data)[i]; dv = (double)iv; break;
-        case BT_INT16: case BT_UINT16: iv = ((const int16_t*)col.data)[i]; dv = (double)iv; break;
-        case BT_INT32: case BT_UINT32: case BT_DATE32: case BT_DICT:
+        case BT_INT16: iv = ((const int16_t*)col.data)[i]; dv = (double)iv; break;
+        case BT_UINT16: iv = ((const uint16_t*)col.data)[i]; dv = (double)iv; break;
+        case BT_INT32: case BT_DATE32: case BT_DICT:
           iv = ((const int32_t*)col.data)[i]; dv = (double)iv; break;
+        case BT_UINT32: iv = ((const uint32_t*)col.data)[i]; dv = (double)iv; break;
         case BT_INT64: case BT_UINT64: case BT_TIMESTAMP_NS:
           iv = ((const int64_t*)col.data)[i]; dv = (double)iv; break;
         case BT_FLOAT32: { float f = ((const float*)col.data)[i]; valid = !(f != f); dv = (double)f; iv = (int64_t)f; break; }
@@ -784,9 +829,11 @@ __global__ void agg_update_fused_kernel(FusedAgg a0, FusedAgg a1, FusedAgg a2,
         switch (col.dtype) {
           case BT_INT8: iv = ((const int8_t*)col.data)[i]; dv = (double)iv; break;
           case BT_UINT8: case BT_BOOL: iv = ((const uint8_t*)col.data)[i]; dv = (double)iv; break;
-          case BT_INT16: case BT_UINT16: iv = ((const int16_t*)col.data)[i]; dv = (double)iv; break;
-          case BT_INT32: case BT_UINT32: case BT_DATE32: case BT_DICT:
+          case BT_INT16: iv = ((const int16_t*)col.data)[i]; dv = (double)iv; break;
+          case BT_UINT16: iv = ((const uint16_t*)col.data)[i]; dv = (double)iv; break;
+          case BT_INT32: case BT_DATE32: case BT_DICT:
             iv = ((const int32_t*)col.data)[i]; dv = (double)iv; break;
+          case BT_UINT32: iv = ((const uint32_t*)col.data)[i]; dv = (double)iv; break;
           case BT_INT64: case BT_UINT64: case BT_TIMESTAMP_NS:
             iv = ((const int64_t*)col.data)[i]; dv = (double)iv; break;
           case BT_FLOAT32: { float f = ((const float*)col.data)[i]; valid = !(f != f); dv = (double)f; iv = (int64_t)f; break; }
@@ -845,9 +892,11 @@ __global__ void agg_update_fused_lds_kernel(
         switch (col.dtype) {
           case BT_INT8: iv = ((const int8_t*)col.data)[i]; dv = (double)iv; break;
           case BT_UINT8: case BT_BOOL: iv = ((const uint8_t*)col.data)[i]; dv = (double)iv; break;
-          case BT_INT16: case BT_UINT16: iv = ((const int16_t*)col.data)[i]; dv = (double)iv; break;
-          case BT_INT32: case BT_UINT32: case BT_DATE32: case BT_DICT:
+          case BT_INT16: iv = ((const int16_t*)col.data)[i]; dv = (double)iv; break;
+          case BT_UINT16: iv = ((const uint16_t*)col.data)[i]; dv = (double)iv; break;
+          case BT_INT32: case BT_DATE32: case BT_DICT:
             iv = ((const int32_t*)col.data)[i]; dv = (double)iv; break;
+          case BT_UINT32: iv = ((const uint32_t*)col.data)[i]; dv = (double)iv; break;
           case BT_INT64: case BT_UINT64: case BT_TIMESTAMP_NS:
             iv = ((const int64_t*)col.data)[i]; dv = (double)iv; break;
           case BT_FLOAT32: { float f = ((const float*)col.data)[i]; valid = !(f != f); dv = (double)f; iv = (int64_t)f; break; }
@@ -1246,11 +1295,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rle_expand", &rle_expand, "parquet RLE/bit-packed hybrid expand");
   m.def("agg_update_fused", &agg_update_fused, "fused multi-aggregate update");
   m.def("groupby_build_packed", &groupby_build_packed,
-        "packed-u64-key hash groupby build");
+        "packed-u64-key hash groupby build", py::arg("keys"),
+        py::arg("chunk_rows") = GB_CHUNK_ROWS,
+        py::arg("max_initial_cap") = GB_PACKED_MAX_INITIAL_CAP);
   m.def("hash_columns", &hash_columns, "multi-column row hash");
   m.def("dt_field", &dt_field, "datetime field extraction");
   m.def("gather_string", &gather_string, "string column gather");
-  m.def("groupby_build", &groupby_build, "hash groupby build");
+  m.def("groupby_build", &groupby_build, "hash groupby build",
+        py::arg("datas"), py::arg("masks"), py::arg("offsets"),
+        py::arg("auxs"), py::arg("dtypes"), py::arg("n"), py::arg("hashes"),
+        py::arg("chunk_rows") = GB_CHUNK_ROWS,
+        py::arg("max_initial_cap") = GB_MAX_INITIAL_CAP);
   m.def("agg_update", &agg_update, "aggregate update");
   m.def("join_build", &join_build, "hash join build");
   m.def("join_probe", &join_probe, "hash join probe");
