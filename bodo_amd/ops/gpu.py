@@ -61,26 +61,33 @@ def _dict_hash_lut(col: Column) -> torch.Tensor:
     return lut
 
 
+def _data_mask8(col: Column):
+    """(data, mask) as the kernels read them: bool values and the validity
+    mask as uint8."""
+    data = col.data
+    if data is not None and data.dtype == torch.bool:
+        data = data.view(torch.uint8)
+    return data, None if col.mask is None else col.mask.view(torch.uint8)
+
+
 def _col_args(cols: Sequence[Column]):
     datas, masks, offsets, auxs, dtypes = [], [], [], [], []
     for c in cols:
+        data, mask8 = _data_mask8(c)
         if c.dtype.kind == TypeKind.STRING:
-            datas.append(c.data if c.data is not None else
+            datas.append(data if data is not None else
                          torch.zeros(0, dtype=torch.uint8, device=c.device))
             offsets.append(c.offsets)
             auxs.append(None)
         elif c.dtype.kind == TypeKind.DICT:
-            datas.append(c.data)
+            datas.append(data)
             offsets.append(None)
             auxs.append(_dict_hash_lut(c))
         else:
-            data = c.data
-            if data.dtype == torch.bool:
-                data = data.view(torch.uint8)
             datas.append(data)
             offsets.append(None)
             auxs.append(None)
-        masks.append(None if c.mask is None else c.mask.view(torch.uint8))
+        masks.append(mask8)
         dtypes.append(int(c.dtype.kind))
     return datas, masks, offsets, auxs, dtypes
 
@@ -323,16 +330,13 @@ def _run_fused(batch, row_gid, ngroups, results):
                 posts.append(("minmax_i64", col))
         if col_for_data is None:
             data = torch.zeros(1, dtype=torch.int8, device=row_gid.device)
-            masks.append(None)
+            mask8 = None
             dtypes.append(int(TypeKind.INT8))
         else:
-            data = col_for_data.data
-            if data.dtype == torch.bool:
-                data = data.view(torch.uint8)
-            masks.append(None if col_for_data.mask is None
-                         else col_for_data.mask.view(torch.uint8))
+            data, mask8 = _data_mask8(col_for_data)
             dtypes.append(int(col_for_data.dtype.kind))
         datas.append(data)
+        masks.append(mask8)
     flat = K.agg_update_fused(datas, masks, dtypes, ops_, init_fs, init_is,
                               wants, row_gid, ngroups)
     shared_cnt = None
@@ -343,8 +347,6 @@ def _run_fused(batch, row_gid, ngroups, results):
     for k, (out_name, col, func) in enumerate(batch):
         acc, cnt = flat[2 * k], flat[2 * k + 1]
         kind, extra = posts[k]
-        nullable = col is not None and ((col.mask is not None)
-                                        or col.dtype.is_float)
         if kind == "cnt_i64":
             results[out_name] = Column(bt.int64, cnt)
         elif kind == "acc_f64":
@@ -359,24 +361,33 @@ def _run_fused(batch, row_gid, ngroups, results):
         elif kind == "mean":
             results[out_name] = Column(bt.float64, acc)
         elif kind == "minmax_f64":
-            empty = cnt == 0
-            out = torch.where(empty, torch.full_like(acc, float("nan")), acc)
-            results[out_name] = Column(bt.float64, out)
+            results[out_name] = _finish_minmax_f64(acc, cnt)
         else:  # minmax_i64
-            if nullable:
-                results[out_name] = Column(bt.float64, torch.where(
-                    cnt == 0,
-                    torch.full((ngroups,), float("nan"), dtype=torch.float64,
-                               device=acc.device),
-                    acc.to(torch.float64)))
-            elif col.dtype.kind == TypeKind.TIMESTAMP_NS:
-                results[out_name] = Column(bt.timestamp_ns, acc)
-            elif col.dtype.kind == TypeKind.DATE32:
-                results[out_name] = Column(bt.date32, acc.to(torch.int32))
-            elif col.dtype.kind == TypeKind.BOOL:
-                results[out_name] = Column(bt.boolean, acc.to(torch.bool))
-            else:
-                results[out_name] = Column(col.dtype, acc.to(col.data.dtype))
+            results[out_name] = _finish_minmax_i64(col, acc, cnt)
+
+
+def _finish_minmax_f64(acc: torch.Tensor, cnt: torch.Tensor) -> Column:
+    """Float min/max: NaN for groups without a valid value."""
+    return Column(bt.float64, torch.where(
+        cnt == 0, torch.full_like(acc, float("nan")), acc))
+
+
+def _finish_minmax_i64(col: Column, acc: torch.Tensor,
+                       cnt: torch.Tensor) -> Column:
+    """Integer min/max of ``col`` from its int64 accumulator: a masked
+    column becomes float64 with NaN for groups without a valid value,
+    anything else returns to the column's own type."""
+    if col.mask is not None:
+        return Column(bt.float64, torch.where(
+            cnt == 0, torch.full_like(acc, float("nan"), dtype=torch.float64),
+            acc.to(torch.float64)))
+    if col.dtype.kind == TypeKind.TIMESTAMP_NS:
+        return Column(bt.timestamp_ns, acc)
+    if col.dtype.kind == TypeKind.DATE32:
+        return Column(bt.date32, acc.to(torch.int32))
+    if col.dtype.kind == TypeKind.BOOL:
+        return Column(bt.boolean, acc.to(torch.bool))
+    return Column(col.dtype, acc.to(col.data.dtype))
 
 
 def _gather_any(col: Column, idx: torch.Tensor) -> Column:
@@ -390,11 +401,11 @@ def _agg_one(col: Optional[Column], row_gid: torch.Tensor, ngroups: int,
     K = kernels()
 
     def upd(op, init_f=0.0, init_i=0, want_count=False):
-        data = col.data if col is not None else torch.zeros(
-            int(row_gid.numel()), dtype=torch.int8, device=row_gid.device)
-        if data.dtype == torch.bool:
-            data = data.view(torch.uint8)
-        mask = None if (col is None or col.mask is None) else col.mask.view(torch.uint8)
+        if col is None:
+            data, mask = torch.zeros(int(row_gid.numel()), dtype=torch.int8,
+                                     device=row_gid.device), None
+        else:
+            data, mask = _data_mask8(col)
         offsets = col.offsets if (col is not None and col.dtype.kind == TypeKind.STRING) else None
         dtype = int(col.dtype.kind) if col is not None else int(TypeKind.INT8)
         return K.agg_update(data, mask, offsets, dtype, row_gid, ngroups,
@@ -407,7 +418,6 @@ def _agg_one(col: Optional[Column], row_gid: torch.Tensor, ngroups: int,
         acc, cnt = upd("count")
         return Column(bt.int64, cnt)
     is_float = col.dtype.is_float
-    nullable = (col.mask is not None) or is_float
     if func == "sum":
         if is_float:
             acc, cnt = upd("sum_f64", want_count=True)
@@ -422,24 +432,10 @@ def _agg_one(col: Optional[Column], row_gid: torch.Tensor, ngroups: int,
         if is_float:
             init = _F64_INF if func == "min" else -_F64_INF
             acc, cnt = upd(f"{func}_f64", init_f=init, want_count=True)
-            empty = cnt == 0
-            acc = torch.where(empty, torch.full_like(acc, float("nan")), acc)
-            return Column(bt.float64, acc)
+            return _finish_minmax_f64(acc, cnt)
         init = _I64_MAX if func == "min" else _I64_MIN
         acc, cnt = upd(f"{func}_i64", init_i=init, want_count=True)
-        if nullable:
-            return Column(bt.float64, torch.where(
-                cnt == 0, torch.full((ngroups,), float("nan"),
-                                     dtype=torch.float64, device=acc.device),
-                acc.to(torch.float64)))
-        out = acc
-        if col.dtype.kind in (TypeKind.TIMESTAMP_NS,):
-            return Column(bt.timestamp_ns, out)
-        if col.dtype.kind == TypeKind.DATE32:
-            return Column(bt.date32, out.to(torch.int32))
-        if col.dtype.kind == TypeKind.BOOL:
-            return Column(bt.boolean, out.to(torch.bool))
-        return Column(col.dtype, out.to(col.data.dtype))
+        return _finish_minmax_i64(col, acc, cnt)
     if func == "mean":
         acc, cnt = upd("sum_f64", want_count=True)
         out = acc / cnt.to(torch.float64)
@@ -464,11 +460,9 @@ def _agg_one(col: Optional[Column], row_gid: torch.Tensor, ngroups: int,
     if func in ("var", "std"):
         acc, cnt = upd("sum_f64", want_count=True)
         # sum of squares via squared input
-        sq = Column(bt.float64, col.data.to(torch.float64) ** 2, col.mask)
-        col2 = sq
-        data = col2.data
-        acc2 = K.agg_update(data, None if col2.mask is None else col2.mask.view(torch.uint8),
-                            None, int(TypeKind.FLOAT64), row_gid, ngroups,
+        sq = col.data.to(torch.float64) ** 2
+        acc2 = K.agg_update(sq, _data_mask8(col)[1], None,
+                            int(TypeKind.FLOAT64), row_gid, ngroups,
                             _AGG_OP["sum_f64"], 0.0, 0, False)[0]
         c = cnt.to(torch.float64)
         var = (acc2 - acc * acc / c) / (c - 1)
@@ -476,7 +470,7 @@ def _agg_one(col: Optional[Column], row_gid: torch.Tensor, ngroups: int,
         return Column(bt.float64, var if func == "var" else var.sqrt())
     if func in ("any", "all"):
         nz = (col.data != 0).to(torch.int64)
-        mask8 = None if col.mask is None else col.mask.view(torch.uint8)
+        mask8 = _data_mask8(col)[1]
         op = "max_i64" if func == "any" else "min_i64"
         init = _I64_MIN if func == "any" else _I64_MAX
         acc, cnt = K.agg_update(nz, mask8, None, int(TypeKind.INT64),
@@ -489,7 +483,7 @@ def _agg_one(col: Optional[Column], row_gid: torch.Tensor, ngroups: int,
         return Column(bt.boolean, out.to(torch.bool))
     if func == "skew":
         x = col.data.to(torch.float64)
-        mask8 = None if col.mask is None else col.mask.view(torch.uint8)
+        mask8 = _data_mask8(col)[1]
         s1, cnt = K.agg_update(x, mask8, None, int(TypeKind.FLOAT64),
                                row_gid, ngroups, _AGG_OP["sum_f64"], 0.0, 0,
                                True)
@@ -508,7 +502,7 @@ def _agg_one(col: Optional[Column], row_gid: torch.Tensor, ngroups: int,
         return Column(bt.float64, g)
     if func == "kurt":
         x = col.data.to(torch.float64)
-        mask8 = None if col.mask is None else col.mask.view(torch.uint8)
+        mask8 = _data_mask8(col)[1]
         s1, cnt = K.agg_update(x, mask8, None, int(TypeKind.FLOAT64),
                                row_gid, ngroups, _AGG_OP["sum_f64"], 0.0, 0,
                                True)
@@ -532,7 +526,7 @@ def _agg_one(col: Optional[Column], row_gid: torch.Tensor, ngroups: int,
     if func == "sem":
         acc, cnt = upd("sum_f64", want_count=True)
         sq = col.data.to(torch.float64) ** 2
-        mask8 = None if col.mask is None else col.mask.view(torch.uint8)
+        mask8 = _data_mask8(col)[1]
         acc2 = K.agg_update(sq, mask8, None, int(TypeKind.FLOAT64), row_gid,
                             ngroups, _AGG_OP["sum_f64"], 0.0, 0, False)[0]
         c = cnt.to(torch.float64)

@@ -89,34 +89,36 @@ DEV_INLINE bool is_valid_at(const ColumnDesc& c, int64_t i) {
   return c.mask == nullptr || c.mask[i];
 }
 
-// null-aware equality of row a and row b of the same column set
-DEV_INLINE bool value_eq(const ColumnDesc& c, int64_t a, int64_t b) {
-  bool va = is_valid_at(c, a), vb = is_valid_at(c, b);
+// null-aware equality of row a of column x and row b of column y; y has
+// x's dtype (x and y are the same column, or a join's two key columns)
+DEV_INLINE bool value_eq2(const ColumnDesc& x, int64_t a, const ColumnDesc& y,
+                          int64_t b) {
+  bool va = is_valid_at(x, a), vb = is_valid_at(y, b);
   if (va != vb) return false;
   if (!va) return true;  // both null
-  switch (c.dtype) {
+  switch (x.dtype) {
     case BT_INT8: case BT_UINT8: case BT_BOOL:
-      return ((const int8_t*)c.data)[a] == ((const int8_t*)c.data)[b];
+      return ((const int8_t*)x.data)[a] == ((const int8_t*)y.data)[b];
     case BT_INT16: case BT_UINT16:
-      return ((const int16_t*)c.data)[a] == ((const int16_t*)c.data)[b];
+      return ((const int16_t*)x.data)[a] == ((const int16_t*)y.data)[b];
     case BT_INT32: case BT_UINT32: case BT_DATE32: case BT_DICT:
-      return ((const int32_t*)c.data)[a] == ((const int32_t*)c.data)[b];
+      return ((const int32_t*)x.data)[a] == ((const int32_t*)y.data)[b];
     case BT_INT64: case BT_UINT64: case BT_TIMESTAMP_NS: case BT_DECIMAL128:
-      return ((const int64_t*)c.data)[a] == ((const int64_t*)c.data)[b];
+      return ((const int64_t*)x.data)[a] == ((const int64_t*)y.data)[b];
     case BT_FLOAT32: {
-      float x = ((const float*)c.data)[a], y = ((const float*)c.data)[b];
-      return (x == y) || (x != x && y != y);
+      float u = ((const float*)x.data)[a], v = ((const float*)y.data)[b];
+      return (u == v) || (u != u && v != v);
     }
     case BT_FLOAT64: {
-      double x = ((const double*)c.data)[a], y = ((const double*)c.data)[b];
-      return (x == y) || (x != x && y != y);
+      double u = ((const double*)x.data)[a], v = ((const double*)y.data)[b];
+      return (u == v) || (u != u && v != v);
     }
     case BT_STRING: {
-      int64_t sa = c.offsets[a], ea = c.offsets[a + 1];
-      int64_t sb = c.offsets[b], eb = c.offsets[b + 1];
+      int64_t sa = x.offsets[a], ea = x.offsets[a + 1];
+      int64_t sb = y.offsets[b], eb = y.offsets[b + 1];
       if (ea - sa != eb - sb) return false;
-      const uint8_t* pa = (const uint8_t*)c.data + sa;
-      const uint8_t* pb = (const uint8_t*)c.data + sb;
+      const uint8_t* pa = (const uint8_t*)x.data + sa;
+      const uint8_t* pb = (const uint8_t*)y.data + sb;
       for (int64_t k = 0; k < ea - sa; ++k)
         if (pa[k] != pb[k]) return false;
       return true;
@@ -125,55 +127,19 @@ DEV_INLINE bool value_eq(const ColumnDesc& c, int64_t a, int64_t b) {
   return false;
 }
 
+DEV_INLINE bool value_eq(const ColumnDesc& c, int64_t a, int64_t b) {
+  return value_eq2(c, a, c, b);
+}
+
 // equality of row a in columns ca[] vs row b in columns cb[] (join probe)
 DEV_INLINE bool rows_eq2(const ColumnDesc* ca, const ColumnDesc* cb, int ncols,
                          int64_t a, int64_t b) {
-  for (int k = 0; k < ncols; ++k) {
-    const ColumnDesc& x = ca[k];
-    const ColumnDesc& y = cb[k];
-    bool va = is_valid_at(x, a), vb = is_valid_at(y, b);
-    if (va != vb) return false;
-    if (!va) continue;  // both null on this key: equal, check next
-    switch (x.dtype) {
-      case BT_INT8: case BT_UINT8: case BT_BOOL:
-        if (((const int8_t*)x.data)[a] != ((const int8_t*)y.data)[b]) return false;
-        break;
-      case BT_INT16: case BT_UINT16:
-        if (((const int16_t*)x.data)[a] != ((const int16_t*)y.data)[b]) return false;
-        break;
-      case BT_INT32: case BT_UINT32: case BT_DATE32: case BT_DICT:
-        if (((const int32_t*)x.data)[a] != ((const int32_t*)y.data)[b]) return false;
-        break;
-      case BT_INT64: case BT_UINT64: case BT_TIMESTAMP_NS: case BT_DECIMAL128:
-        if (((const int64_t*)x.data)[a] != ((const int64_t*)y.data)[b]) return false;
-        break;
-      case BT_FLOAT32: {
-        float u = ((const float*)x.data)[a], v = ((const float*)y.data)[b];
-        if (!((u == v) || (u != u && v != v))) return false;
-        break;
-      }
-      case BT_FLOAT64: {
-        double u = ((const double*)x.data)[a], v = ((const double*)y.data)[b];
-        if (!((u == v) || (u != u && v != v))) return false;
-        break;
-      }
-      case BT_STRING: {
-        int64_t sa = x.offsets[a], ea = x.offsets[a + 1];
-        int64_t sb = y.offsets[b], eb = y.offsets[b + 1];
-        if (ea - sa != eb - sb) return false;
-        const uint8_t* pa = (const uint8_t*)x.data + sa;
-        const uint8_t* pb = (const uint8_t*)y.data + sb;
-        for (int64_t t = 0; t < ea - sa; ++t)
-          if (pa[t] != pb[t]) return false;
-        break;
-      }
-      default:
-        return false;
-    }
-  }
+  for (int k = 0; k < ncols; ++k)
+    if (!value_eq2(ca[k], a, cb[k], b)) return false;
   return true;
 }
 
+// equality of rows a and b of the same column set (group keys)
 DEV_INLINE bool rows_eq(const ColumnDesc* cols, int ncols, int64_t a, int64_t b) {
   for (int k = 0; k < ncols; ++k)
     if (!value_eq(cols[k], a, b)) return false;

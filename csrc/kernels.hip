@@ -349,33 +349,6 @@ static int64_t grown_cap(int64_t cap, int64_t occupied, int64_t n) {
   return want;
 }
 
-// two-pass group-id assignment: pass 1 counts occupied slots per block
-// (no atomics), host cumsums 2048 values, pass 2 assigns gids via an LDS
-// counter (one global atomic total: zero).  Replaces a single-global-counter
-// atomicAdd that measured 43% of NYC-taxi Q1 step time at 300M rows.
-__global__ void gb_count_kernel(const uint32_t* __restrict__ slots,
-                                int64_t chunk, int64_t cap,
-                                int64_t* __restrict__ block_counts) {
-  int64_t start = (int64_t)blockIdx.x * chunk;
-  int64_t stop = min(start + chunk, cap);
-  int64_t local = 0;
-  for (int64_t s = start + threadIdx.x; s < stop; s += blockDim.x) {
-    local += (slots[s] != 0u);
-  }
-  __shared__ int64_t red[256];
-  red[threadIdx.x] = local;
-  __syncthreads();
-  for (int w = blockDim.x / 2; w > 0; w >>= 1) {
-    if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) block_counts[blockIdx.x] = red[0];
-}
-
-__global__ void gb_rowgid_kernel(const uint32_t* __restrict__ row_slot,
-                                 const int32_t* __restrict__ slot_gid,
-                                 int32_t* __restrict__ row_gid, int64_t n);
-
 // Packed-key fast path: keys pre-packed into one u64 (< 2^63), slots hold
 // the KEY itself (CAS, sentinel ~0) so probing never dereferences candidate
 // rows or a hash array; the slot hash is computed in-kernel.
@@ -415,34 +388,35 @@ __global__ void gb_insert_packed_kernel(const int64_t* __restrict__ keys,
   }
 }
 
-__global__ void gb_assign_gid_packed_kernel(
-    const unsigned long long* __restrict__ slot_keys,
-    const uint32_t* __restrict__ slot_rows, int64_t chunk, int64_t cap,
-    const int64_t* __restrict__ block_base, int32_t* __restrict__ slot_gid,
-    int64_t* __restrict__ uniq_rows) {
-  int64_t start = (int64_t)blockIdx.x * chunk;
-  int64_t stop = min(start + chunk, cap);
-  __shared__ int lds_cnt;
-  if (threadIdx.x == 0) lds_cnt = 0;
-  __syncthreads();
-  int64_t base = block_base[blockIdx.x];
-  for (int64_t s = start + threadIdx.x; s < stop; s += blockDim.x) {
-    if (slot_keys[s] != PACKED_EMPTY) {
-      int32_t gid = (int32_t)(base + atomicAdd(&lds_cnt, 1));
-      slot_gid[s] = gid;
-      uniq_rows[gid] = (int64_t)slot_rows[s] - 1;
-    }
-  }
-}
+// What the passes after the insert need to know about a table: whether slot
+// s holds a group, and the first row of that group.
+struct GenericSlots {  // gb_insert_kernel: slot = row + 1, 0 = empty
+  const uint32_t* slots;
+  DEV_INLINE bool occupied(int64_t s) const { return slots[s] != 0u; }
+  DEV_INLINE int64_t row(int64_t s) const { return (int64_t)slots[s] - 1; }
+};
 
-__global__ void gb_count_packed_kernel(
-    const unsigned long long* __restrict__ slot_keys, int64_t chunk,
-    int64_t cap, int64_t* __restrict__ block_counts) {
+struct PackedSlots {  // gb_insert_packed_kernel: key slots + row + 1 beside
+  const unsigned long long* slot_keys;
+  const uint32_t* slot_rows;
+  DEV_INLINE bool occupied(int64_t s) const {
+    return slot_keys[s] != PACKED_EMPTY;
+  }
+  DEV_INLINE int64_t row(int64_t s) const { return (int64_t)slot_rows[s] - 1; }
+};
+
+// two-pass group-id assignment: pass 1 counts occupied slots per block
+// (no atomics), host cumsums 2048 values, pass 2 assigns gids via an LDS
+// counter (one global atomic total: zero).  Replaces a single-global-counter
+// atomicAdd that measured 43% of NYC-taxi Q1 step time at 300M rows.
+template <typename Slots>
+__global__ void gb_count_kernel(const Slots table, int64_t chunk, int64_t cap,
+                                int64_t* __restrict__ block_counts) {
   int64_t start = (int64_t)blockIdx.x * chunk;
   int64_t stop = min(start + chunk, cap);
   int64_t local = 0;
   for (int64_t s = start + threadIdx.x; s < stop; s += blockDim.x) {
-    local += (slot_keys[s] != PACKED_EMPTY);
+    local += table.occupied(s);
   }
   __shared__ int64_t red[256];
   red[threadIdx.x] = local;
@@ -454,82 +428,9 @@ __global__ void gb_count_packed_kernel(
   if (threadIdx.x == 0) block_counts[blockIdx.x] = red[0];
 }
 
-std::vector<torch::Tensor> groupby_build_packed(torch::Tensor keys,
-                                                int64_t chunk_rows,
-                                                int64_t max_initial_cap) {
-  auto dev = keys.device();
-  int64_t n = keys.numel();
-  check_build_limits(chunk_rows, max_initial_cap);
-  int block = 256;
-  // 2^25 slots x 8 B = 256 MB: Infinity-Cache resident; grow on pressure
-  int64_t cap = 16;
-  while (cap < 2 * n) cap <<= 1;
-  if (cap > max_initial_cap) cap = max_initial_cap;
-  auto row_slot = torch::empty({n}, torch::dtype(torch::kInt32).device(dev));
-  torch::Tensor slot_keys, slot_rows;
-  while (true) {
-    slot_keys = torch::full({cap}, -1, torch::dtype(torch::kInt64).device(dev));
-    slot_rows = torch::empty({cap}, torch::dtype(torch::kInt32).device(dev));
-    bool grown = false;
-    // Invariant (see insert_step): while cap < 2n a launch adds at most
-    // cap/2 - 1 keys and starts with occupied <= cap/2, so occupied < cap
-    // always holds and every probe finds a free slot or its key.
-    const int64_t step = insert_step(chunk_rows, cap, n);
-    for (int64_t start = 0; start < n; start += step) {
-      int64_t cnt = std::min(step, n - start);
-      hipLaunchKernelGGL(gb_insert_packed_kernel, dim3(grid_for(cnt, block)),
-                         dim3(block), 0, cur_stream(),
-                         (const int64_t*)keys.data_ptr() + start,
-                         (unsigned long long*)slot_keys.data_ptr(),
-                         (uint32_t*)slot_rows.data_ptr(), (uint64_t)(cap - 1),
-                         (uint32_t*)row_slot.data_ptr() + start, cnt, start);
-      CHECK_HIP(hipGetLastError());
-      if (start + cnt < n && cap < 2 * n) {
-        int64_t occupied = (slot_keys != -1).sum().item<int64_t>();
-        if (occupied * 2 > cap) {
-          cap = grown_cap(cap, occupied, n);
-          grown = true;
-          break;
-        }
-      }
-    }
-    if (!grown) break;
-  }
-  int nblocks = 2048;
-  int64_t chunk = (cap + nblocks - 1) / nblocks;
-  auto block_counts = torch::zeros({nblocks},
-                                   torch::dtype(torch::kInt64).device(dev));
-  hipLaunchKernelGGL(gb_count_packed_kernel, dim3(nblocks), dim3(block), 0,
-                     cur_stream(),
-                     (const unsigned long long*)slot_keys.data_ptr(), chunk,
-                     cap, (int64_t*)block_counts.data_ptr());
-  CHECK_HIP(hipGetLastError());
-  auto block_base = torch::zeros({nblocks}, torch::dtype(torch::kInt64).device(dev));
-  auto bb_tail = block_base.slice(0, 1, nblocks);
-  at::cumsum_out(bb_tail, block_counts.slice(0, 0, nblocks - 1), 0);
-  int64_t ngroups = block_counts.sum().item<int64_t>();
-  auto slot_gid = torch::empty({cap}, torch::dtype(torch::kInt32).device(dev));
-  auto uniq_rows = torch::empty({std::max<int64_t>(ngroups, 1)},
-                                torch::dtype(torch::kInt64).device(dev));
-  hipLaunchKernelGGL(gb_assign_gid_packed_kernel, dim3(nblocks), dim3(block),
-                     0, cur_stream(),
-                     (const unsigned long long*)slot_keys.data_ptr(),
-                     (const uint32_t*)slot_rows.data_ptr(), chunk, cap,
-                     (const int64_t*)block_base.data_ptr(),
-                     (int32_t*)slot_gid.data_ptr(),
-                     (int64_t*)uniq_rows.data_ptr());
-  CHECK_HIP(hipGetLastError());
-  auto row_gid = torch::empty({n}, torch::dtype(torch::kInt32).device(dev));
-  hipLaunchKernelGGL(gb_rowgid_kernel, dim3(grid_for(n, block)), dim3(block),
-                     0, cur_stream(), (const uint32_t*)row_slot.data_ptr(),
-                     (const int32_t*)slot_gid.data_ptr(),
-                     (int32_t*)row_gid.data_ptr(), n);
-  CHECK_HIP(hipGetLastError());
-  return {row_gid, uniq_rows.slice(0, 0, std::max<int64_t>(ngroups, 0))};
-}
-
-__global__ void gb_assign_gid_kernel(const uint32_t* __restrict__ slots,
-                                     int64_t chunk, int64_t cap,
+template <typename Slots>
+__global__ void gb_assign_gid_kernel(const Slots table, int64_t chunk,
+                                     int64_t cap,
                                      const int64_t* __restrict__ block_base,
                                      int32_t* __restrict__ slot_gid,
                                      int64_t* __restrict__ uniq_rows) {
@@ -540,11 +441,10 @@ __global__ void gb_assign_gid_kernel(const uint32_t* __restrict__ slots,
   __syncthreads();
   int64_t base = block_base[blockIdx.x];
   for (int64_t s = start + threadIdx.x; s < stop; s += blockDim.x) {
-    uint32_t v = slots[s];
-    if (v != 0u) {
+    if (table.occupied(s)) {
       int32_t gid = (int32_t)(base + atomicAdd(&lds_cnt, 1));
       slot_gid[s] = gid;
-      uniq_rows[gid] = (int64_t)v - 1;
+      uniq_rows[gid] = table.row(s);
     }
   }
 }
@@ -555,32 +455,29 @@ __global__ void gb_rowgid_kernel(const uint32_t* __restrict__ row_slot,
   GRID_STRIDE_LOOP(i, n) { row_gid[i] = slot_gid[row_slot[i]]; }
 }
 
-std::vector<torch::Tensor> groupby_build(
-    std::vector<torch::Tensor> datas,
-    std::vector<c10::optional<torch::Tensor>> masks,
-    std::vector<c10::optional<torch::Tensor>> offsets,
-    std::vector<c10::optional<torch::Tensor>> auxs,
-    std::vector<int64_t> dtypes, int64_t n, torch::Tensor hashes,
-    int64_t chunk_rows, int64_t max_initial_cap) {
-  auto dev = datas[0].device();
-  auto ds = build_descset(datas, masks, offsets, auxs, dtypes, n);
+// Skeleton shared by both group builds.  The caller supplies its table:
+//   alloc(cap)                    allocate an empty table of cap slots
+//   insert(cap, start, cnt, rs)   launch the insert of rows [start, start+cnt),
+//                                 rs = row_slot + start
+//   occupied()                    slots in use (device sync)
+//   view()                        GenericSlots / PackedSlots of the table
+// Insert in chunks, checking the load factor between chunks; grow and
+// re-insert when it crosses 1/2.  While the table is smaller than 2n slots a
+// chunk is at most cap/2 - 1 rows (insert_step), each followed by a device
+// sync and a count of the table.
+template <typename Alloc, typename Insert, typename Occupied, typename View>
+static std::vector<torch::Tensor> build_groups(
+    int64_t n, const torch::Device& dev, int64_t chunk_rows,
+    int64_t max_initial_cap, Alloc alloc, Insert insert, Occupied occupied,
+    View view) {
   check_build_limits(chunk_rows, max_initial_cap);
-  // Start with an Infinity-Cache-resident table (2^26 slots = 256 MB):
-  // the random atomicCAS probes then hit L3 instead of HBM (guide §2).
-  // Insert in chunks, checking the load factor between chunks; grow 8x and
-  // re-insert when it crosses 1/2 (few groupbys exceed 32M groups/rank).
-  // While the table is smaller than 2n slots a chunk is at most cap/2 - 1
-  // rows (insert_step), each followed by a device sync and a count of the
-  // table: n above 2^25 rows takes several launches where chunk_rows alone
-  // would give one.
+  int block = 256;
   int64_t cap = 16;
   while (cap < 2 * n) cap <<= 1;
   if (cap > max_initial_cap) cap = max_initial_cap;
-  int block = 256;
   auto row_slot = torch::empty({n}, torch::dtype(torch::kInt32).device(dev));
-  torch::Tensor slots;
   while (true) {
-    slots = torch::zeros({cap}, torch::dtype(torch::kInt32).device(dev));
+    alloc(cap);
     bool grown = false;
     // Invariant (see insert_step): while cap < 2n a launch adds at most
     // cap/2 - 1 groups and starts with occupied <= cap/2, so occupied < cap
@@ -588,18 +485,12 @@ std::vector<torch::Tensor> groupby_build(
     const int64_t step = insert_step(chunk_rows, cap, n);
     for (int64_t start = 0; start < n; start += step) {
       int64_t cnt = std::min(step, n - start);
-      hipLaunchKernelGGL(gb_insert_kernel, dim3(grid_for(cnt, block)),
-                         dim3(block), 0, cur_stream(), ds.ptr(),
-                         (int)datas.size(),
-                         (const uint64_t*)hashes.data_ptr() + start,
-                         (uint32_t*)slots.data_ptr(), (uint64_t)(cap - 1),
-                         (uint32_t*)row_slot.data_ptr() + start, cnt, start,
-                         (const uint64_t*)hashes.data_ptr());
+      insert(cap, start, cnt, (uint32_t*)row_slot.data_ptr() + start);
       CHECK_HIP(hipGetLastError());
       if (start + cnt < n && cap < 2 * n) {
-        int64_t occupied = torch::count_nonzero(slots).item<int64_t>();
-        if (occupied * 2 > cap) {
-          cap = grown_cap(cap, occupied, n);
+        int64_t occ = occupied();
+        if (occ * 2 > cap) {
+          cap = grown_cap(cap, occ, n);
           grown = true;
           break;  // rebuild from scratch at the bigger capacity
         }
@@ -607,24 +498,25 @@ std::vector<torch::Tensor> groupby_build(
     }
     if (!grown) break;
   }
-  auto slot_gid = torch::empty({cap}, torch::dtype(torch::kInt32).device(dev));
-  auto uniq_rows = torch::empty({n > 0 ? n : 1},
-                                torch::dtype(torch::kInt64).device(dev));
+  auto table = view();
   int nblocks = 2048;
   int64_t chunk = (cap + nblocks - 1) / nblocks;
   auto block_counts = torch::zeros({nblocks},
                                    torch::dtype(torch::kInt64).device(dev));
-  hipLaunchKernelGGL(gb_count_kernel, dim3(nblocks), dim3(block), 0,
-                     cur_stream(), (const uint32_t*)slots.data_ptr(), chunk,
-                     cap, (int64_t*)block_counts.data_ptr());
+  hipLaunchKernelGGL(gb_count_kernel<decltype(table)>, dim3(nblocks),
+                     dim3(block), 0, cur_stream(), table, chunk, cap,
+                     (int64_t*)block_counts.data_ptr());
   CHECK_HIP(hipGetLastError());
   auto block_base = torch::zeros({nblocks}, torch::dtype(torch::kInt64).device(dev));
   auto bb_tail = block_base.slice(0, 1, nblocks);
   at::cumsum_out(bb_tail, block_counts.slice(0, 0, nblocks - 1), 0);
   int64_t ngroups = block_counts.sum().item<int64_t>();
-  hipLaunchKernelGGL(gb_assign_gid_kernel, dim3(nblocks), dim3(block), 0,
-                     cur_stream(), (const uint32_t*)slots.data_ptr(), chunk,
-                     cap, (const int64_t*)block_base.data_ptr(),
+  auto slot_gid = torch::empty({cap}, torch::dtype(torch::kInt32).device(dev));
+  auto uniq_rows = torch::empty({std::max<int64_t>(ngroups, 1)},
+                                torch::dtype(torch::kInt64).device(dev));
+  hipLaunchKernelGGL(gb_assign_gid_kernel<decltype(table)>, dim3(nblocks),
+                     dim3(block), 0, cur_stream(), table, chunk, cap,
+                     (const int64_t*)block_base.data_ptr(),
                      (int32_t*)slot_gid.data_ptr(),
                      (int64_t*)uniq_rows.data_ptr());
   CHECK_HIP(hipGetLastError());
@@ -637,6 +529,66 @@ std::vector<torch::Tensor> groupby_build(
   return {row_gid, uniq_rows.slice(0, 0, ngroups)};
 }
 
+std::vector<torch::Tensor> groupby_build_packed(torch::Tensor keys,
+                                                int64_t chunk_rows,
+                                                int64_t max_initial_cap) {
+  auto dev = keys.device();
+  torch::Tensor slot_keys, slot_rows;
+  // 2^25 slots x 8 B = 256 MB: Infinity-Cache resident; grow on pressure
+  return build_groups(
+      keys.numel(), dev, chunk_rows, max_initial_cap,
+      [&](int64_t cap) {
+        slot_keys = torch::full({cap}, -1, torch::dtype(torch::kInt64).device(dev));
+        slot_rows = torch::empty({cap}, torch::dtype(torch::kInt32).device(dev));
+      },
+      [&](int64_t cap, int64_t start, int64_t cnt, uint32_t* row_slot) {
+        hipLaunchKernelGGL(gb_insert_packed_kernel, dim3(grid_for(cnt, 256)),
+                           dim3(256), 0, cur_stream(),
+                           (const int64_t*)keys.data_ptr() + start,
+                           (unsigned long long*)slot_keys.data_ptr(),
+                           (uint32_t*)slot_rows.data_ptr(), (uint64_t)(cap - 1),
+                           row_slot, cnt, start);
+      },
+      [&] { return (slot_keys != -1).sum().item<int64_t>(); },
+      [&] {
+        return PackedSlots{(const unsigned long long*)slot_keys.data_ptr(),
+                           (const uint32_t*)slot_rows.data_ptr()};
+      });
+}
+
+std::vector<torch::Tensor> groupby_build(
+    std::vector<torch::Tensor> datas,
+    std::vector<c10::optional<torch::Tensor>> masks,
+    std::vector<c10::optional<torch::Tensor>> offsets,
+    std::vector<c10::optional<torch::Tensor>> auxs,
+    std::vector<int64_t> dtypes, int64_t n, torch::Tensor hashes,
+    int64_t chunk_rows, int64_t max_initial_cap) {
+  auto dev = datas[0].device();
+  auto ds = build_descset(datas, masks, offsets, auxs, dtypes, n);
+  torch::Tensor slots;
+  // Start with an Infinity-Cache-resident table (2^26 slots = 256 MB):
+  // the random atomicCAS probes then hit L3 instead of HBM (guide §2).
+  // Growth is 8x at a time (few groupbys exceed 32M groups/rank); n above
+  // 2^25 rows takes several insert launches where chunk_rows alone would
+  // give one.
+  return build_groups(
+      n, dev, chunk_rows, max_initial_cap,
+      [&](int64_t cap) {
+        slots = torch::zeros({cap}, torch::dtype(torch::kInt32).device(dev));
+      },
+      [&](int64_t cap, int64_t start, int64_t cnt, uint32_t* row_slot) {
+        hipLaunchKernelGGL(gb_insert_kernel, dim3(grid_for(cnt, 256)),
+                           dim3(256), 0, cur_stream(), ds.ptr(),
+                           (int)datas.size(),
+                           (const uint64_t*)hashes.data_ptr() + start,
+                           (uint32_t*)slots.data_ptr(), (uint64_t)(cap - 1),
+                           row_slot, cnt, start,
+                           (const uint64_t*)hashes.data_ptr());
+      },
+      [&] { return torch::count_nonzero(slots).item<int64_t>(); },
+      [&] { return GenericSlots{(const uint32_t*)slots.data_ptr()}; });
+}
+
 // ------------------------------------------------------------ agg update
 
 enum AggOp : int {
@@ -645,10 +597,79 @@ enum AggOp : int {
   AGG_FIRST_ROW = 8, AGG_LAST_ROW = 9, AGG_PROD_F64 = 10,
 };
 
-template <typename T>
-DEV_INLINE double load_as_f64(const T* p, int64_t i) { return (double)p[i]; }
+// accumulators hold doubles for these ops and int64 for all others
+__host__ __device__ inline bool is_f64_acc(int64_t op) {
+  return op == AGG_SUM_F64 || op == AGG_MIN_F64 || op == AGG_MAX_F64 ||
+         op == AGG_PROD_F64;
+}
 
-// value loader switch: returns value as double or int64 depending on op
+// One column value as both double and int64 (the op picks one).  Null rows
+// and float NaNs are invalid; STRING and DECIMAL128 load nothing (only
+// their validity is counted).
+struct AggValue {
+  bool valid;
+  double dv;
+  int64_t iv;
+};
+
+DEV_INLINE AggValue agg_load(const ColumnDesc& col, int64_t i) {
+  AggValue v = {is_valid_at(col, i), 0.0, 0};
+  if (!v.valid) return v;
+  switch (col.dtype) {
+    case BT_INT8: v.iv = ((const int8_t*)col.data)[i]; v.dv = (double)v.iv; break;
+    case BT_UINT8: case BT_BOOL: v.iv = ((const uint8_t*)col.data)[i]; v.dv = (double)v.iv; break;
+    case BT_INT16: v.iv = ((const int16_t*)col.data)[i]; v.dv = (double)v.iv; break;
+    case BT_UINT16: v.iv = ((const uint16_t*)col.data)[i]; v.dv = (double)v.iv; break;
+    case BT_INT32: case BT_DATE32: case BT_DICT:
+      v.iv = ((const int32_t*)col.data)[i]; v.dv = (double)v.iv; break;
+    case BT_UINT32: v.iv = ((const uint32_t*)col.data)[i]; v.dv = (double)v.iv; break;
+    case BT_INT64: case BT_UINT64: case BT_TIMESTAMP_NS:
+      v.iv = ((const int64_t*)col.data)[i]; v.dv = (double)v.iv; break;
+    case BT_FLOAT32: {
+      float f = ((const float*)col.data)[i];
+      v.valid = !(f != f);
+      v.dv = (double)f; v.iv = (int64_t)f;
+      break;
+    }
+    case BT_FLOAT64: {
+      double f = ((const double*)col.data)[i];
+      v.valid = !(f != f);
+      v.dv = f; v.iv = (int64_t)f;
+      break;
+    }
+  }
+  return v;
+}
+
+// Fold one contribution into accumulator slot `a`, which lives in global
+// memory or in LDS (inlined, so the compiler picks the atomic's address
+// space from the call site).  SIZE and COUNT only count; AGG_PROD_F64 has
+// no LDS form and is handled by agg_update_kernel alone.
+DEV_INLINE void agg_apply(int op, double* a, double dv, int64_t iv,
+                          int64_t row) {
+  switch (op) {
+    case AGG_SUM_F64: atomicAdd(a, dv); break;
+    case AGG_SUM_I64: atomicAdd((unsigned long long*)a, (unsigned long long)iv); break;
+    case AGG_MIN_F64: atomic_min_f64(a, dv); break;
+    case AGG_MAX_F64: atomic_max_f64(a, dv); break;
+    case AGG_MIN_I64: atomic_min_i64((int64_t*)a, iv); break;
+    case AGG_MAX_I64: atomic_max_i64((int64_t*)a, iv); break;
+    case AGG_FIRST_ROW: atomic_min_i64((int64_t*)a, row); break;
+    case AGG_LAST_ROW: atomic_max_i64((int64_t*)a, row); break;
+  }
+}
+
+// Merge one block's LDS partial for group g (value bits `part`, `c` rows
+// counted) into the global accumulators.  Groups the block never saw still
+// hold the op's init value and are skipped.
+DEV_INLINE void agg_merge(int op, void* acc, int64_t* cnt, int g, double part,
+                          long long c) {
+  if (c == 0) return;
+  if (cnt != nullptr) atomicAdd((unsigned long long*)&cnt[g], (unsigned long long)c);
+  int64_t bits = __double_as_longlong(part);
+  agg_apply(op, (double*)acc + g, part, bits, bits);
+}
+
 __global__ void agg_update_kernel(const ColumnDesc col,
                                   const int32_t* __restrict__ row_gid,
                                   int op, void* __restrict__ acc,
@@ -659,56 +680,19 @@ __global__ void agg_update_kernel(const ColumnDesc col,
       atomicAdd((unsigned long long*)&cnt[g], 1ull);
       continue;
     }
-    bool valid = is_valid_at(col, i);
-    double dv = 0.0;
-    int64_t iv = 0;
-    if (valid) {
-      switch (col.dtype) {
-        case BT_INT8: iv = ((const int8_t*)col.data)[i]; dv = (double)iv; break;
-        case BT_UINT8: case BT_BOOL: iv = ((const uint8_t*)col.data)[i]; dv = (double)iv; break;
-        case BT_INT16: iv = ((const int16_t*)col.data)[i]; dv = (double)iv; break;
-        case BT_UINT16: iv = ((const uint16_t*)col.data)[i]; dv = (double)iv; break;
-        case BT_INT32: case BT_DATE32: case BT_DICT:
-          iv = ((const int32_t*)col.data)[i]; dv = (double)iv; break;
-        case BT_UINT32: iv = ((const uint32_t*)col.data)[i]; dv = (double)iv; break;
-        case BT_INT64: case BT_UINT64: case BT_TIMESTAMP_NS:
-          iv = ((const int64_t*)col.data)[i]; dv = (double)iv; break;
-        case BT_FLOAT32: {
-          float f = ((const float*)col.data)[i];
-          valid = !(f != f);
-          dv = (double)f; iv = (int64_t)f;
-          break;
-        }
-        case BT_FLOAT64: {
-          double f = ((const double*)col.data)[i];
-          valid = !(f != f);
-          dv = f; iv = (int64_t)f;
-          break;
-        }
-      }
-    }
-    if (!valid) continue;
-    switch (op) {
-      case AGG_SUM_F64: atomicAdd((double*)acc + g, dv); break;
-      case AGG_SUM_I64: atomicAdd((unsigned long long*)acc + g, (unsigned long long)iv); break;
-      case AGG_COUNT: break;  // counted below
-      case AGG_MIN_F64: atomic_min_f64((double*)acc + g, dv); break;
-      case AGG_MAX_F64: atomic_max_f64((double*)acc + g, dv); break;
-      case AGG_MIN_I64: atomic_min_i64((int64_t*)acc + g, iv); break;
-      case AGG_MAX_I64: atomic_max_i64((int64_t*)acc + g, iv); break;
-      case AGG_FIRST_ROW: atomic_min_i64((int64_t*)acc + g, (int64_t)i); break;
-      case AGG_LAST_ROW: atomic_max_i64((int64_t*)acc + g, (int64_t)i); break;
-      case AGG_PROD_F64: {
-        // CAS-loop multiply
-        unsigned long long* a = (unsigned long long*)acc + g;
-        unsigned long long old = *a, assumed;
-        do {
-          assumed = old;
-          double nv = __longlong_as_double(assumed) * dv;
-          old = atomicCAS(a, assumed, (unsigned long long)__double_as_longlong(nv));
-        } while (old != assumed);
-        break;
-      }
+    AggValue v = agg_load(col, i);
+    if (!v.valid) continue;
+    if (op == AGG_PROD_F64) {
+      // CAS-loop multiply
+      unsigned long long* a = (unsigned long long*)acc + g;
+      unsigned long long old = *a, assumed;
+      do {
+        assumed = old;
+        double nv = __longlong_as_double(assumed) * v.dv;
+        old = atomicCAS(a, assumed, (unsigned long long)__double_as_longlong(nv));
+      } while (old != assumed);
+    } else {
+      agg_apply(op, (double*)acc + g, v.dv, v.iv, i);
     }
     if (cnt != nullptr) atomicAdd((unsigned long long*)&cnt[g], 1ull);
   }
@@ -728,73 +712,29 @@ __global__ void agg_update_lds_kernel(const ColumnDesc col,
                                       double init_f, int64_t init_i) {
   __shared__ double lacc[LDS_AGG_MAX_GROUPS];
   __shared__ long long lcnt[LDS_AGG_MAX_GROUPS];
-  bool f64_acc = (op == AGG_SUM_F64 || op == AGG_MIN_F64 || op == AGG_MAX_F64);
   for (int g = threadIdx.x; g < ngroups; g += blockDim.x) {
-    lacc[g] = f64_acc ? init_f : __longlong_as_double(init_i);
+    lacc[g] = is_f64_acc(op) ? init_f : __longlong_as_double(init_i);
     lcnt[g] = 0;
   }
   __syncthreads();
   GRID_STRIDE_LOOP(i, n) {
     int32_t g = row_gid[i];
-    if (op == AGG_SIZE) {
-      atomicAdd((unsigned long long*)&lcnt[g], 1ull);
-      continue;
+    if (op != AGG_SIZE) {
+      AggValue v = agg_load(col, i);
+      if (!v.valid) continue;
+      agg_apply(op, &lacc[g], v.dv, v.iv, i);
     }
-    bool valid = is_valid_at(col, i);
-    double dv = 0.0;
-    int64_t iv = 0;
-    if (valid) {
-      switch (col.dtype) {
-        case BT_INT8: iv = ((const int8_t*)col.data)[i]; dv = (double)iv; break;
-        case BT_UINT8: case BT_BOOL: iv = ((const uint8_t*)col.data)[i]; dv = (double)iv; break;
-        case BT_INT16: iv = ((const int16_t*)col.data)[i]; dv = (double)iv; break;
-        case BT_UINT16: iv = ((const uint16_t*)col.data)[i]; dv = (double)iv; break;
-        case BT_INT32: case BT_DATE32: case BT_DICT:
-          iv = ((const int32_t*)col.data)[i]; dv = (double)iv; break;
-        case BT_UINT32: iv = ((const uint32_t*)col.data)[i]; dv = (double)iv; break;
-        case BT_INT64: case BT_UINT64: case BT_TIMESTAMP_NS:
-          iv = ((const int64_t*)col.data)[i]; dv = (double)iv; break;
-        case BT_FLOAT32: { float f = ((const float*)col.data)[i]; valid = !(f != f); dv = (double)f; iv = (int64_t)f; break; }
-        case BT_FLOAT64: { double f = ((const double*)col.data)[i]; valid = !(f != f); dv = f; iv = (int64_t)f; break; }
-      }
-    }
-    if (!valid) continue;
-    switch (op) {
-      case AGG_SUM_F64: atomicAdd(&lacc[g], dv); break;
-      case AGG_SUM_I64: atomicAdd((unsigned long long*)&lacc[g], (unsigned long long)iv); break;
-      case AGG_COUNT: break;
-      case AGG_MIN_F64: atomic_min_f64(&lacc[g], dv); break;
-      case AGG_MAX_F64: atomic_max_f64(&lacc[g], dv); break;
-      case AGG_MIN_I64: atomic_min_i64((int64_t*)&lacc[g], iv); break;
-      case AGG_MAX_I64: atomic_max_i64((int64_t*)&lacc[g], iv); break;
-      case AGG_FIRST_ROW: atomic_min_i64((int64_t*)&lacc[g], (int64_t)i); break;
-      case AGG_LAST_ROW: atomic_max_i64((int64_t*)&lacc[g], (int64_t)i); break;
-    }
+    // counted even when cnt == nullptr: the merge skips groups with c == 0
     atomicAdd((unsigned long long*)&lcnt[g], 1ull);
   }
   __syncthreads();
-  // merge block partials into global accumulators
-  for (int g = threadIdx.x; g < ngroups; g += blockDim.x) {
-    long long c = lcnt[g];
-    if (cnt != nullptr && c) atomicAdd((unsigned long long*)&cnt[g], (unsigned long long)c);
-    if (op == AGG_SIZE || op == AGG_COUNT) continue;
-    if (c == 0) continue;
-    switch (op) {
-      case AGG_SUM_F64: atomicAdd((double*)acc + g, lacc[g]); break;
-      case AGG_SUM_I64: atomicAdd((unsigned long long*)acc + g,
-                                  (unsigned long long)__double_as_longlong(lacc[g])); break;
-      case AGG_MIN_F64: atomic_min_f64((double*)acc + g, lacc[g]); break;
-      case AGG_MAX_F64: atomic_max_f64((double*)acc + g, lacc[g]); break;
-      case AGG_MIN_I64: atomic_min_i64((int64_t*)acc + g, __double_as_longlong(lacc[g])); break;
-      case AGG_MAX_I64: atomic_max_i64((int64_t*)acc + g, __double_as_longlong(lacc[g])); break;
-      case AGG_FIRST_ROW: atomic_min_i64((int64_t*)acc + g, __double_as_longlong(lacc[g])); break;
-      case AGG_LAST_ROW: atomic_max_i64((int64_t*)acc + g, __double_as_longlong(lacc[g])); break;
-    }
-  }
+  for (int g = threadIdx.x; g < ngroups; g += blockDim.x)
+    agg_merge(op, acc, cnt, g, lacc[g], lcnt[g]);
 }
 
 // fused multi-aggregate: one pass over row_gid updating up to 4 aggregates
-// (taxi Q1: count + sum + count in ONE read of the gid array)
+// (taxi Q1: count + sum + count in ONE read of the gid array).  Ops are
+// AGG_SUM_F64..AGG_SIZE only; agg_update_fused rejects the rest.
 #define MAX_FUSED_AGGS 4
 
 struct FusedAgg {
@@ -814,42 +754,15 @@ __global__ void agg_update_fused_kernel(FusedAgg a0, FusedAgg a1, FusedAgg a2,
   GRID_STRIDE_LOOP(i, n) {
     int32_t g = row_gid[i];
     for (int k = 0; k < n_aggs; ++k) {
-      const ColumnDesc& col = aggs[k].col;
       int op = aggs[k].op;
-      void* acc = aggs[k].acc;
       int64_t* cnt = aggs[k].cnt;
       if (op == AGG_SIZE) {
         atomicAdd((unsigned long long*)&cnt[g], 1ull);
         continue;
       }
-      bool valid = is_valid_at(col, i);
-      double dv = 0.0;
-      int64_t iv = 0;
-      if (valid) {
-        switch (col.dtype) {
-          case BT_INT8: iv = ((const int8_t*)col.data)[i]; dv = (double)iv; break;
-          case BT_UINT8: case BT_BOOL: iv = ((const uint8_t*)col.data)[i]; dv = (double)iv; break;
-          case BT_INT16: iv = ((const int16_t*)col.data)[i]; dv = (double)iv; break;
-          case BT_UINT16: iv = ((const uint16_t*)col.data)[i]; dv = (double)iv; break;
-          case BT_INT32: case BT_DATE32: case BT_DICT:
-            iv = ((const int32_t*)col.data)[i]; dv = (double)iv; break;
-          case BT_UINT32: iv = ((const uint32_t*)col.data)[i]; dv = (double)iv; break;
-          case BT_INT64: case BT_UINT64: case BT_TIMESTAMP_NS:
-            iv = ((const int64_t*)col.data)[i]; dv = (double)iv; break;
-          case BT_FLOAT32: { float f = ((const float*)col.data)[i]; valid = !(f != f); dv = (double)f; iv = (int64_t)f; break; }
-          case BT_FLOAT64: { double f = ((const double*)col.data)[i]; valid = !(f != f); dv = f; iv = (int64_t)f; break; }
-        }
-      }
-      if (!valid) continue;
-      switch (op) {
-        case AGG_SUM_F64: atomicAdd((double*)acc + g, dv); break;
-        case AGG_SUM_I64: atomicAdd((unsigned long long*)acc + g, (unsigned long long)iv); break;
-        case AGG_COUNT: break;
-        case AGG_MIN_F64: atomic_min_f64((double*)acc + g, dv); break;
-        case AGG_MAX_F64: atomic_max_f64((double*)acc + g, dv); break;
-        case AGG_MIN_I64: atomic_min_i64((int64_t*)acc + g, iv); break;
-        case AGG_MAX_I64: atomic_max_i64((int64_t*)acc + g, iv); break;
-      }
+      AggValue v = agg_load(aggs[k].col, i);
+      if (!v.valid) continue;
+      agg_apply(op, (double*)aggs[k].acc + g, v.dv, v.iv, i);
       if (cnt != nullptr) atomicAdd((unsigned long long*)&cnt[g], 1ull);
     }
   }
@@ -868,75 +781,43 @@ __global__ void agg_update_fused_lds_kernel(
   long long* lcnt = (long long*)(smem + (size_t)n_aggs * ngroups);
   for (int j = threadIdx.x; j < n_aggs * ngroups; j += blockDim.x) {
     int k = j / ngroups;
-    int op = aggs[k].op;
-    bool f64_acc = (op == AGG_SUM_F64 || op == AGG_MIN_F64 || op == AGG_MAX_F64);
-    lacc[j] = f64_acc ? aggs[k].init_f : __longlong_as_double(aggs[k].init_i);
+    lacc[j] = is_f64_acc(aggs[k].op) ? aggs[k].init_f
+                                     : __longlong_as_double(aggs[k].init_i);
     lcnt[j] = 0;
   }
   __syncthreads();
   GRID_STRIDE_LOOP(i, n) {
     int32_t g = row_gid[i];
     for (int k = 0; k < n_aggs; ++k) {
-      double* la = lacc + (size_t)k * ngroups;
-      long long* lc = lcnt + (size_t)k * ngroups;
       int op = aggs[k].op;
-      if (op == AGG_SIZE) {
-        atomicAdd((unsigned long long*)&lc[g], 1ull);
-        continue;
+      if (op != AGG_SIZE) {
+        AggValue v = agg_load(aggs[k].col, i);
+        if (!v.valid) continue;
+        agg_apply(op, &lacc[(size_t)k * ngroups + g], v.dv, v.iv, i);
       }
-      const ColumnDesc& col = aggs[k].col;
-      bool valid = is_valid_at(col, i);
-      double dv = 0.0;
-      int64_t iv = 0;
-      if (valid) {
-        switch (col.dtype) {
-          case BT_INT8: iv = ((const int8_t*)col.data)[i]; dv = (double)iv; break;
-          case BT_UINT8: case BT_BOOL: iv = ((const uint8_t*)col.data)[i]; dv = (double)iv; break;
-          case BT_INT16: iv = ((const int16_t*)col.data)[i]; dv = (double)iv; break;
-          case BT_UINT16: iv = ((const uint16_t*)col.data)[i]; dv = (double)iv; break;
-          case BT_INT32: case BT_DATE32: case BT_DICT:
-            iv = ((const int32_t*)col.data)[i]; dv = (double)iv; break;
-          case BT_UINT32: iv = ((const uint32_t*)col.data)[i]; dv = (double)iv; break;
-          case BT_INT64: case BT_UINT64: case BT_TIMESTAMP_NS:
-            iv = ((const int64_t*)col.data)[i]; dv = (double)iv; break;
-          case BT_FLOAT32: { float f = ((const float*)col.data)[i]; valid = !(f != f); dv = (double)f; iv = (int64_t)f; break; }
-          case BT_FLOAT64: { double f = ((const double*)col.data)[i]; valid = !(f != f); dv = f; iv = (int64_t)f; break; }
-        }
-      }
-      if (!valid) continue;
-      switch (op) {
-        case AGG_SUM_F64: atomicAdd(&la[g], dv); break;
-        case AGG_SUM_I64: atomicAdd((unsigned long long*)&la[g], (unsigned long long)iv); break;
-        case AGG_COUNT: break;
-        case AGG_MIN_F64: atomic_min_f64(&la[g], dv); break;
-        case AGG_MAX_F64: atomic_max_f64(&la[g], dv); break;
-        case AGG_MIN_I64: atomic_min_i64((int64_t*)&la[g], iv); break;
-        case AGG_MAX_I64: atomic_max_i64((int64_t*)&la[g], iv); break;
-      }
-      atomicAdd((unsigned long long*)&lc[g], 1ull);
+      atomicAdd((unsigned long long*)&lcnt[(size_t)k * ngroups + g], 1ull);
     }
   }
   __syncthreads();
   for (int j = threadIdx.x; j < n_aggs * ngroups; j += blockDim.x) {
     int k = j / ngroups;
-    int g = j - k * ngroups;
-    int op = aggs[k].op;
-    void* acc = aggs[k].acc;
-    long long c = lcnt[j];
-    if (aggs[k].cnt != nullptr && c)
-      atomicAdd((unsigned long long*)&aggs[k].cnt[g], (unsigned long long)c);
-    if (op == AGG_SIZE || op == AGG_COUNT) continue;
-    if (c == 0) continue;
-    switch (op) {
-      case AGG_SUM_F64: atomicAdd((double*)acc + g, lacc[j]); break;
-      case AGG_SUM_I64: atomicAdd((unsigned long long*)acc + g,
-                                  (unsigned long long)__double_as_longlong(lacc[j])); break;
-      case AGG_MIN_F64: atomic_min_f64((double*)acc + g, lacc[j]); break;
-      case AGG_MAX_F64: atomic_max_f64((double*)acc + g, lacc[j]); break;
-      case AGG_MIN_I64: atomic_min_i64((int64_t*)acc + g, __double_as_longlong(lacc[j])); break;
-      case AGG_MAX_I64: atomic_max_i64((int64_t*)acc + g, __double_as_longlong(lacc[j])); break;
-    }
+    agg_merge(aggs[k].op, aggs[k].acc, aggs[k].cnt, j - k * ngroups, lacc[j],
+              lcnt[j]);
   }
+}
+
+// accumulator filled with the op's init value, plus the valid-row count
+// when asked for or when the count is the op's result (else undefined)
+static std::pair<torch::Tensor, torch::Tensor> alloc_agg(
+    int64_t op, int64_t ngroups, double init_f, int64_t init_i,
+    bool want_count, const torch::Device& dev) {
+  torch::Tensor acc = is_f64_acc(op)
+      ? torch::full({ngroups}, init_f, torch::dtype(torch::kFloat64).device(dev))
+      : torch::full({ngroups}, init_i, torch::dtype(torch::kInt64).device(dev));
+  torch::Tensor cnt;
+  if (want_count || op == AGG_SIZE || op == AGG_COUNT)
+    cnt = torch::zeros({ngroups}, torch::dtype(torch::kInt64).device(dev));
+  return {acc, cnt};
 }
 
 // returns per agg: [acc, cnt?] pairs flattened
@@ -951,27 +832,23 @@ std::vector<torch::Tensor> agg_update_fused(
   int64_t n = row_gid.numel();
   int n_aggs = (int)datas.size();
   TORCH_CHECK(n_aggs >= 1 && n_aggs <= MAX_FUSED_AGGS);
+  for (int k = 0; k < n_aggs; ++k)
+    TORCH_CHECK(ops[k] >= AGG_SUM_F64 && ops[k] <= AGG_SIZE,
+                "agg_update_fused: unsupported op ", ops[k]);
   std::vector<torch::Tensor> out;
   FusedAgg fas[MAX_FUSED_AGGS] = {};
   for (int k = 0; k < n_aggs; ++k) {
-    int64_t op = ops[k];
-    bool f64_acc = (op == AGG_SUM_F64 || op == AGG_MIN_F64 || op == AGG_MAX_F64);
-    torch::Tensor acc = f64_acc
-        ? torch::full({ngroups}, init_fs[k], torch::dtype(torch::kFloat64).device(dev))
-        : torch::full({ngroups}, init_is[k], torch::dtype(torch::kInt64).device(dev));
-    torch::Tensor cnt;
-    if (want_counts[k] || op == AGG_SIZE || op == AGG_COUNT) {
-      cnt = torch::zeros({ngroups}, torch::dtype(torch::kInt64).device(dev));
-    }
+    auto [acc, cnt] = alloc_agg(ops[k], ngroups, init_fs[k], init_is[k],
+                                want_counts[k] != 0, dev);
     fas[k].col = make_desc(datas[k], masks[k], c10::nullopt, c10::nullopt,
                            dtypes[k], n);
-    fas[k].op = (int)op;
+    fas[k].op = (int)ops[k];
     fas[k].acc = acc.data_ptr();
     fas[k].cnt = cnt.defined() ? (int64_t*)cnt.data_ptr() : nullptr;
     fas[k].init_f = init_fs[k];
     fas[k].init_i = init_is[k];
     out.push_back(acc);
-    out.push_back(cnt.defined() ? cnt : torch::Tensor());
+    out.push_back(cnt.defined() ? cnt : torch::empty({0}));
   }
   int block = 256;
   size_t lds_bytes = (size_t)n_aggs * (size_t)ngroups * 16;
@@ -986,9 +863,7 @@ std::vector<torch::Tensor> agg_update_fused(
                        fas[3], n_aggs, (const int32_t*)row_gid.data_ptr(), n);
   }
   CHECK_HIP(hipGetLastError());
-  std::vector<torch::Tensor> cleaned;
-  for (auto& t : out) cleaned.push_back(t.defined() ? t : torch::empty({0}));
-  return cleaned;
+  return out;
 }
 
 std::vector<torch::Tensor> agg_update(
@@ -996,22 +871,10 @@ std::vector<torch::Tensor> agg_update(
     c10::optional<torch::Tensor> offsets, int64_t dtype,
     torch::Tensor row_gid, int64_t ngroups, int64_t op, double init_f,
     int64_t init_i, bool want_count) {
-  auto dev = data.device();
   int64_t n = row_gid.numel();
-  torch::Tensor acc;
-  bool f64_acc = (op == AGG_SUM_F64 || op == AGG_MIN_F64 || op == AGG_MAX_F64 ||
-                  op == AGG_PROD_F64);
-  if (f64_acc) {
-    acc = torch::full({ngroups}, init_f, torch::dtype(torch::kFloat64).device(dev));
-  } else {
-    acc = torch::full({ngroups}, init_i, torch::dtype(torch::kInt64).device(dev));
-  }
-  torch::Tensor cnt;
-  int64_t* cnt_ptr = nullptr;
-  if (want_count || op == AGG_SIZE || op == AGG_COUNT) {
-    cnt = torch::zeros({ngroups}, torch::dtype(torch::kInt64).device(dev));
-    cnt_ptr = (int64_t*)cnt.data_ptr();
-  }
+  auto [acc, cnt] = alloc_agg(op, ngroups, init_f, init_i, want_count,
+                              data.device());
+  int64_t* cnt_ptr = cnt.defined() ? (int64_t*)cnt.data_ptr() : nullptr;
   ColumnDesc col = make_desc(data, mask, offsets, c10::nullopt, dtype, n);
   int block = 256;
   bool lds_ok = ngroups <= LDS_AGG_MAX_GROUPS && op != AGG_PROD_F64;

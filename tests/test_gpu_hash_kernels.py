@@ -8,6 +8,7 @@ The sizes pick the kernel, nothing here asserts which one ran:
 ``agg_update_fused`` above ``n_aggs * ngroups * 16 B == 48 KiB``.
 """
 
+import datetime
 from collections import Counter
 from functools import lru_cache
 
@@ -299,6 +300,83 @@ def test_groupby_local_unsigned_vs_pandas():
                 got1.to_numpy(),
                 exp_all[f"{c}_{f}"].to_numpy().astype(np.int64),
                 err_msg=f"_agg_one {c} {f}")
+
+
+_FINISH_COLS = ("i32", "i64", "ts", "d32", "b", "f64")
+
+
+def _finisher_frame():
+    """257 rows in 5 groups, one column per branch of the min/max
+    finishers: masked int32 and float64 with NaN (group 3 all null in
+    both), unmasked int64, timestamp, date32 and bool."""
+    rng = np.random.default_rng(63)
+    n = 257
+    k = rng.integers(0, 5, n).astype(np.int64)
+    k[:5] = np.arange(5)
+    null = k == 3
+    i32 = pd.array(rng.integers(-1000, 1000, n).astype(np.int32),
+                   dtype="Int32")
+    i32[null | (rng.random(n) < 0.2)] = pd.NA
+    f64 = rng.integers(-4096, 4096, n) / 1024.0
+    f64[null | (rng.random(n) < 0.2)] = np.nan
+    day0 = datetime.date(2020, 1, 1)
+    b = rng.random(n) < 0.5
+    b[k == 1] = True
+    b[k == 2] = False
+    return pd.DataFrame({
+        "k": k, "i32": i32,
+        "i64": rng.integers(-2**40, 2**40, n).astype(np.int64),
+        "ts": pd.to_datetime(rng.integers(0, 2**60, n)),
+        "d32": [day0 + datetime.timedelta(days=int(d))
+                for d in rng.integers(-4000, 4000, n)],
+        "b": b, "f64": f64,
+    })
+
+
+def test_groupby_minmax_finishers_fused_and_agg_one():
+    """min and max of every finisher branch through the fused path and
+    through ``_agg_one``: the two agree exactly in value and type, and both
+    match pandas (min/max do not depend on the order of the atomics)."""
+    from bodo_amd.core.table import Table
+    from bodo_amd.core.types import TypeKind
+    from bodo_amd.ops import gpu
+
+    df = _finisher_frame()
+    t = Table.from_pandas(df, device="cuda")
+    assert t.column("i32").mask is not None and t.column("i64").mask is None
+    assert t.column("d32").dtype.kind == TypeKind.DATE32
+    aggs = [(f"{c}_{f}", c, f) for c in _FINISH_COLS for f in ("min", "max")]
+    exp = df.groupby("k").agg(**{o: (c, f) for o, c, f in aggs}).reset_index()
+    assert exp.loc[3, ["i32_min", "f64_max"]].isna().all()
+    for o in ("i32_min", "i32_max"):  # a masked column comes back as float64
+        exp[o] = exp[o].astype("float64")
+
+    fused = gpu.groupby_local(t, ["k"], aggs)
+    row_gid, uniq_rows = gpu.groupby_build([t.column("k")])
+    ngroups = int(uniq_rows.numel())
+    one = Table(["k"] + [o for o, _, _ in aggs],
+                [gpu._gather_any(t.column("k"), uniq_rows)] +
+                [gpu._agg_one(t.column(c), row_gid, ngroups, f, uniq_rows, t)
+                 for _, c, f in aggs], ngroups)
+    for o, _, _ in aggs:
+        a, b = fused.column(o), one.column(o)
+        assert a.dtype == b.dtype and a.data.dtype == b.data.dtype, o
+        assert (a.mask is None) and (b.mask is None), o
+        _assert_bits_equal(a.data, b.data.cpu().numpy(), o)
+    for got in (fused, one):
+        pd.testing.assert_frame_equal(_sorted(got.to_pandas(), "k"), exp,
+                                      check_dtype=False, check_exact=True)
+
+
+@pytest.mark.parametrize("op", [8, 9, 10])
+def test_agg_update_fused_rejects_unsupported_ops(op):
+    """first_row, last_row and prod_f64 have no fused form: rejected on the
+    host, before any launch."""
+    gid = torch.arange(16, dtype=torch.int32, device="cuda") % 2
+    data = torch.ones(16, dtype=torch.float64, device="cuda")
+    with pytest.raises(RuntimeError):
+        _K().agg_update_fused([data], [None], [R.FLOAT64], [op], [0.0], [0],
+                              [1], gid, 2)
 
 
 def test_hash_unsigned_matches_cpu():
