@@ -8,8 +8,14 @@ column chunk: snappy (or uncompressed) v1 data pages decompress one wave per
 page, definition levels expand to a validity mask (nullable columns),
 then PLAIN fixed-width values, PLAIN BYTE_ARRAY strings or RLE_DICTIONARY
 codes are assembled into a Column.  The pipelined shard reader decompresses
-the pages of every column chunk of a few row groups in one launch.  Chunks
-outside this path (other codecs, v2 pages, BOOLEAN/INT96/FIXED_LEN, mixed
+the pages of every column chunk of a few row groups in one launch, and
+decodes chunks that hold no nulls by their footer statistics (PLAIN
+fixed-width values, string-dictionary codes) straight into whole-shard
+columns allocated once: one pq_values_multi call per group checks each
+page's definition levels and writes its values in place, so such columns
+need no mask, no per-chunk launches and no concatenation.  Integer and
+date32 columns take val_range from the footer's min/max.  Chunks outside
+these paths (other codecs, v2 pages, BOOLEAN/INT96/FIXED_LEN, mixed
 plain/dict) take the older per-page route and then the host Arrow decoder.
 """
 
@@ -183,7 +189,7 @@ class _PinnedUploader:
 _UPLOADER = _PinnedUploader()
 
 # decode-path counters (tests assert the batched path actually ran)
-STATS = {"batched": 0, "slow": 0}
+STATS = {"batched": 0, "slow": 0, "direct": 0}
 # CPU tests flip this with simulated kernels monkeypatched in
 FORCE_BATCHED = False
 
@@ -200,6 +206,13 @@ _PAGEPTR_DT = np.dtype([
     ("src", np.uint64), ("dst", np.uint64), ("src_len", np.int32),
     ("dst_len", np.int32), ("flags", np.int32), ("pad", np.int32),
 ])
+# page table entry of K.pq_values_multi (struct ValPage, csrc/parquet.hip)
+_VALPAGE_DT = np.dtype([
+    ("page", np.uint64), ("out", np.uint64), ("lut", np.uint64),
+    ("dst_len", np.int32), ("nv", np.int32), ("kind", np.int32),
+    ("flags", np.int32), ("code_lim", np.int32), ("pad", np.int32),
+])
+_PQK_CODES = 0  # ValPage.kind of dictionary codes; PLAIN: element size
 # row groups whose column chunks share one decompress launch in the
 # pipelined reader (1..32 measured: profiles/decode_parallel_snappy.md)
 _GROUP_ROW_GROUPS = 16
@@ -285,9 +298,11 @@ class _ChunkReader:
                         prep.scratch)
         return self._finish_batched(prep, device, field)
 
-    def _prepare_batched(self, device) -> Optional[_Prepared]:
+    def _prepare_batched(self, device,
+                         upload_metas: bool = True) -> Optional[_Prepared]:
         """First half: headers, dictionary page, page table, scratch.
-        None when the chunk is outside the batched path."""
+        None when the chunk is outside the batched path.  A chunk decoded
+        in place needs no device copy of its page table (upload_metas)."""
         if torch.device(device).type != "cuda" and not FORCE_BATCHED:
             return None  # batched kernels are device-only (tests simulate)
         comp = self.meta.compression
@@ -367,7 +382,8 @@ class _ChunkReader:
         else:
             src_dev = _UPLOADER.upload(
                 np.frombuffer(self.buf, dtype=np.uint8), device)
-        metas_dev = torch.from_numpy(metas.view(np.uint8)).to(device)
+        metas_dev = torch.from_numpy(metas.view(np.uint8)).to(device) \
+            if upload_metas else None
         scratch_size = int(((d_usize + 7) & ~7).sum()) + 16
         scratch = torch.empty(scratch_size, dtype=torch.uint8, device=device)
         prep = _Prepared()
@@ -649,7 +665,188 @@ def read_shard_gpu(path: str, columns, ctx) -> Optional[Table]:
     return ops.concat_tables(out_tables)
 
 
-_NSLOTS = int(os.environ.get("BODO_AMD_READ_THREADS", "8"))
+# reader threads = pinned staging slots.  The stream waits for these threads
+# (page cache -> pinned memory), not the other way round: 8 / 12 / 14 threads
+# gave 1003-1165 / 839-867 / 841-897 ms per flagship step
+# (profiles/decode_in_place.md)
+_NSLOTS = int(os.environ.get("BODO_AMD_READ_THREADS", "12"))
+
+# decode eligible chunks straight into whole-shard columns (off: every
+# chunk takes the per-chunk finish and the pieces are concatenated)
+DIRECT = os.environ.get("BODO_AMD_PQ_DIRECT", "1") != "0"
+
+_DICT_ENCODINGS = {"RLE_DICTIONARY", "PLAIN_DICTIONARY"}
+_DIRECT_PLAIN = {"INT32": torch.int32, "INT64": torch.int64,
+                 "FLOAT": torch.float32, "DOUBLE": torch.float64}
+
+
+class _DictUnifier:
+    """Dictionary of a whole shard column, grown chunk by chunk on the
+    host: values in first-seen order across the chunks in shard order,
+    which is what ops.concat_columns makes of the chunks' dictionaries."""
+
+    def __init__(self):
+        self.values: list = []
+        self.index: dict = {}
+
+    def add(self, dict_vals) -> Optional[np.ndarray]:
+        """Take in one chunk's dictionary.  Returns the int32 table from
+        the chunk's codes to unified codes, or None when every code already
+        is its unified code (the chunk's dictionary is a prefix of the
+        unified one, or extends it)."""
+        lut = np.empty(len(dict_vals), dtype=np.int32)
+        same = True
+        for i, v in enumerate(dict_vals):
+            j = self.index.get(v)
+            if j is None:
+                j = len(self.values)
+                self.index[v] = j
+                self.values.append(v)
+            lut[i] = j
+            same = same and j == i
+        return None if same else lut
+
+    def dictionary(self) -> pa.Array:
+        return pa.array(self.values, type=pa.large_string())
+
+
+def _stat_int(v) -> Optional[int]:
+    import datetime
+
+    if isinstance(v, bool):
+        return None
+    if isinstance(v, (int, np.integer)):
+        return int(v)
+    if isinstance(v, datetime.date) and not isinstance(v, datetime.datetime):
+        return (v - datetime.date(1970, 1, 1)).days
+    return None
+
+
+def _val_range_from_meta(chunk_metas, t: pa.DataType
+                         ) -> Optional[Tuple[int, int]]:
+    """(min, max) of an integer or date32 column from the footer statistics
+    of its chunks; None unless every chunk carries min and max."""
+    if not (pa.types.is_integer(t) or pa.types.is_date32(t)):
+        return None
+    lo = hi = None
+    for cm in chunk_metas:
+        st = cm.statistics if cm.is_stats_set else None
+        if st is None or not st.has_min_max:
+            return None
+        a, b = _stat_int(st.min), _stat_int(st.max)
+        if a is None or b is None:
+            return None
+        lo = a if lo is None else min(lo, a)
+        hi = b if hi is None else max(hi, b)
+    if lo is None:
+        return None
+    return lo, hi
+
+
+def _direct_chunk_kind(cm, field: pa.Field) -> Optional[str]:
+    """'plain' or 'dict' when the footer says this chunk can be decoded in
+    place: no nulls by its statistics (or a required field), PLAIN
+    fixed-width values or a string dictionary.  Page headers can still
+    disagree later (v2 pages, a dictionary that overflowed to PLAIN)."""
+    if cm.compression not in ("SNAPPY", "UNCOMPRESSED"):
+        return None
+    if field.nullable:
+        st = cm.statistics if cm.is_stats_set else None
+        if st is None or not st.has_null_count or st.null_count != 0:
+            return None
+    has_dict = bool(_DICT_ENCODINGS & set(cm.encodings))
+    t = field.type
+    if cm.physical_type in _DIRECT_PLAIN:
+        if has_dict:
+            return None
+        if cm.physical_type == "INT32":
+            ok = pa.types.is_int32(t) or pa.types.is_date32(t)
+        elif cm.physical_type == "INT64":
+            ok = pa.types.is_int64(t) or pa.types.is_timestamp(t)
+        elif cm.physical_type == "FLOAT":
+            ok = pa.types.is_float32(t)
+        else:
+            ok = pa.types.is_float64(t)
+        return "plain" if ok else None
+    if pa.types.is_dictionary(t):  # written from a dictionary array
+        t = t.value_type
+    if cm.physical_type == "BYTE_ARRAY" and has_dict and (
+            pa.types.is_string(t) or pa.types.is_large_string(t)):
+        return "dict"
+    return None
+
+
+class _DirectCol:
+    """A shard column that its chunks are decoded into in place."""
+
+    __slots__ = ("kind", "esize", "data", "field", "unifier")
+
+
+def _plan_direct(items, n_rgs: int, total_rows: int, device) -> dict:
+    """name -> _DirectCol for the columns whose every chunk is eligible by
+    the footer; their whole-shard tensors are allocated here, once."""
+    by_name: dict = {}
+    for it in items:
+        by_name.setdefault(it[2].path_in_schema, []).append(it)
+    plan = {}
+    for name, its in by_name.items():
+        field = its[0][3]
+        if len(its) != n_rgs or any(it[3].type != field.type or
+                                    it[3].nullable != field.nullable
+                                    for it in its):
+            continue
+        kinds = {_direct_chunk_kind(it[2], it[3]) for it in its}
+        phys = {it[2].physical_type for it in its}
+        if len(kinds) != 1 or None in kinds or len(phys) != 1:
+            continue
+        dc = _DirectCol()
+        dc.kind = kinds.pop()
+        dc.field = field
+        if dc.kind == "plain":
+            tdt = _DIRECT_PLAIN[phys.pop()]
+            dc.unifier = None
+        else:
+            tdt = torch.int32
+            dc.unifier = _DictUnifier()
+        dc.data = torch.empty(total_rows, dtype=tdt, device=device)
+        dc.esize = dc.data.element_size()
+        plan[name] = dc
+    return plan
+
+
+class _TableUploader:
+    """Pinned staging ring for the page tables of a group: the tables are
+    written into a pinned buffer and copied with non_blocking=True, so the
+    consumer thread never waits for the chunk copies queued before them.
+    An event per buffer guards its reuse."""
+
+    def __init__(self, n: int = 4):
+        self.bufs = [None] * n
+        self.events = [None] * n
+        self.i = 0
+
+    def upload(self, host_u8: np.ndarray, dev_out: torch.Tensor) -> None:
+        n = len(host_u8)
+        i = self.i
+        self.i = (i + 1) % len(self.bufs)
+        ev = self.events[i]
+        if ev is not None:
+            ev.synchronize()  # the copy out of this buffer is done
+            self.events[i] = None
+        buf = self.bufs[i]
+        if buf is None or buf.numel() < n:
+            buf = torch.empty(max(n, 1 << 21), dtype=torch.uint8,
+                              pin_memory=True)
+            self.bufs[i] = buf
+        buf.numpy()[:n] = host_u8
+        dev_out.copy_(buf[:n], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self.events[i] = ev
+
+
+_TABLES = _TableUploader()
+_RETRY = object()  # the direct read gave up: read again without it
 
 
 def _read_pieces_pipelined(my, columns, ctx) -> Optional[Table]:
@@ -660,18 +857,50 @@ def _read_pieces_pipelined(my, columns, ctx) -> Optional[Table]:
     parses page headers (C++), snips the small dictionary page, issues the
     async H2D copy and releases the slot for reuse once the copy's event
     fires.  Chunks are decoded in groups of _GROUP_ROW_GROUPS row groups:
-    each is prepared as it arrives, one decompress launch covers the pages
-    of the whole group, then each chunk is finished.  Disk read overlaps
-    PCIe upload and decode kernels of other chunks (reference role: bodo/io/parquet_reader.cpp prefetch +
+    each is prepared as it arrives and one decompress launch covers the
+    pages of the whole group.
+
+    Columns whose every chunk is free of nulls by the footer statistics and
+    holds PLAIN fixed-width values or string-dictionary codes are *direct*:
+    their whole-shard tensors are allocated up front from the footer's row
+    counts, and one pq_values_multi call per group checks each page's
+    definition levels and writes its values at the page's place in the
+    shard column (dictionary codes through a per-chunk table into the
+    shard's unified dictionary).  Both page tables and the code tables of a
+    group go up in one pinned, non-blocking copy.  The kernels report bad
+    pages through one error word read once at the end; if it is set, or
+    page headers contradict the footer, the shard is read again with the
+    direct path off.  All other chunks are finished one by one as before
+    and joined per column with ops.concat_columns.  Integer and date32
+    columns get val_range from the footer's min/max on both routes.
+
+    Disk read overlaps PCIe upload and decode kernels of other chunks
+    (reference role: bodo/io/parquet_reader.cpp prefetch +
     _io_cpu_thread_pool.cpp)."""
+    if DIRECT:
+        saved = {k: STATS.get(k, 0) for k in ("batched", "slow", "direct")}
+        out = _read_pieces_impl(my, columns, ctx, True)
+        if out is not _RETRY:
+            return out
+        STATS.update(saved)
+    return _read_pieces_impl(my, columns, ctx, False)
+
+
+def _read_pieces_impl(my, columns, ctx, direct: bool):
+    import threading
     import time
     from concurrent.futures import ThreadPoolExecutor
 
     import bodo_amd_kernels as K
 
+    from .. import ops
+
     device = ctx.device
-    items = []  # (fp, rg, cm, field, start, size, first_of_rg)
+    # (fp, rg, cm, field, start, size, first_of_rg, names, first row of the
+    #  row group in the shard, rows of the row group)
+    items = []
     pf_cache = {}
+    total_rows = 0
     for fp, rg in my:
         pf = pf_cache.get(fp)
         if pf is None:
@@ -688,26 +917,36 @@ def _read_pieces_pipelined(my, columns, ctx) -> Optional[Table]:
                 continue
             start, size = _chunk_range(cm)
             items.append((fp, rg, cm, schema.field(cm.path_in_schema),
-                          start, size, first, names))
+                          start, size, first, names, total_rows,
+                          int(rgm.num_rows)))
             first = False
+        total_rows += int(rgm.num_rows)
     if not items:
         return None
-
-    import threading
+    plan = _plan_direct(items, len(my), total_rows, device) if direct else {}
+    err = torch.zeros(1, dtype=torch.int32, device=device) if plan else None
 
     slots = [{"t": None, "np": None, "ev": None} for _ in range(_NSLOTS)]
-    # DETERMINISTIC slot assignment: task k uses slot k % N, gated by a
-    # per-slot semaphore released when the consumer finishes the slot's
-    # previous occupant (task k-N).  A shared free-slot queue deadlocked:
-    # workers for tasks AHEAD of the consumer could hoard every released
-    # slot while the consumer waited on the one starved task (observed as
-    # all threads parked in slot_q.get on 600-chunk shards).
-    sems = [threading.Semaphore(1) for _ in range(_NSLOTS)]
+    # DETERMINISTIC slot assignment: task k uses slot k % N once the
+    # consumer is done with the slot's previous occupant, task k-N.  The
+    # consumer takes tasks in order, so the gate is one counter of tasks it
+    # has let go of.  A shared free-slot queue deadlocked: workers for tasks
+    # AHEAD of the consumer could hoard every released slot while the
+    # consumer waited on the one starved task (observed as all threads
+    # parked in slot_q.get on 600-chunk shards); a semaphore per slot let
+    # task k+N take the slot from a task k that was slow to wake up.
+    gate = threading.Condition()
+    released = [0]  # tasks 0 .. released-1 no longer need their slots
+    stop = [False]  # the consumer left early: fetches return at once
 
     def fetch(idx):
-        fp, rg, cm, field, start, size, first, names = items[idx]
+        fp, start, size = items[idx][0], items[idx][4], items[idx][5]
         i = idx % _NSLOTS
-        sems[i].acquire()
+        with gate:
+            while released[0] <= idx - _NSLOTS and not stop[0]:
+                gate.wait()
+        if stop[0]:
+            return i
         t0 = time.perf_counter()  # read time proper: not the slot wait
         s = slots[i]
         if s["ev"] is not None:
@@ -726,22 +965,39 @@ def _read_pieces_pipelined(my, columns, ctx) -> Optional[Table]:
     ex = ThreadPoolExecutor(max_workers=_NSLOTS)
     # (event, chunk count) per flushed group or per-chunk fallback decode
     inflight: List[Tuple[torch.cuda.Event, int]] = []
-    # chunks of the current group: [name, names-of-its-row-group, first,
-    # reader, field, prepared-or-None, Column-or-None]
+    # chunks of the current group: [name, reader, field, prepared-or-None,
+    # Column-or-None, direct (column, first row, code table) or None]
     group: list = []
     group_rgs = 0
-    rg_tables: List[Table] = []
+    pieces: dict = {}  # name -> Columns of the non-direct chunks, in order
+    metas_of: dict = {}  # name -> chunk metadata, for val_range
+    field_of: dict = {}
+    seen_names: List[str] = []
 
     def flush():
-        """One decompress launch for every prepared chunk of the group,
-        then the second half of each chunk's decode, then the tables."""
+        """One decompress launch for every prepared chunk of the group and
+        one values call for its direct chunks, then the second half of
+        each other chunk's decode."""
         nonlocal group, group_rgs
         if not group:
             return True
         t0 = time.perf_counter()
-        preps = [e[5] for e in group if e[5] is not None]
+        preps = [e[3] for e in group if e[3] is not None]
+        directs = [e for e in group if e[5] is not None]
         if preps:
-            tbl = np.zeros(sum(p.n_pages for p in preps), dtype=_PAGEPTR_DT)
+            n_dec = sum(p.n_pages for p in preps)
+            n_val = sum(e[3].n_pages for e in directs)
+            dec_bytes = n_dec * _PAGEPTR_DT.itemsize
+            val_bytes = n_val * _VALPAGE_DT.itemsize
+            lut_at, nbytes = [], dec_bytes + val_bytes
+            for e in directs:
+                lut = e[5][2]
+                lut_at.append(nbytes)
+                if lut is not None:
+                    nbytes += (lut.nbytes + 7) & ~7
+            host = np.zeros(nbytes, dtype=np.uint8)
+            blob = torch.empty(nbytes, dtype=torch.uint8, device=device)
+            tbl = host[:dec_bytes].view(_PAGEPTR_DT)
             at = 0
             for p in preps:
                 v = tbl[at:at + p.n_pages]
@@ -751,50 +1007,72 @@ def _read_pieces_pipelined(my, columns, ctx) -> Optional[Table]:
                 v["dst_len"] = p.metas["dst_len"]
                 v["flags"] = p.metas["flags"] & _PQF_SNAPPY
                 at += p.n_pages
-            tbl_dev = torch.from_numpy(tbl.view(np.uint8)).to(device)
-            K.pq_decompress_multi(tbl_dev, len(tbl))
+            vt = host[dec_bytes:dec_bytes + val_bytes].view(_VALPAGE_DT)
+            at = 0
+            for e, la in zip(directs, lut_at):
+                p = e[3]
+                dc, row0, lut = e[5]
+                v = vt[at:at + p.n_pages]
+                v["page"] = p.scratch.data_ptr() + p.metas["dst_off"]
+                v["out"] = dc.data.data_ptr() + \
+                    (row0 + p.metas["val_off"]) * dc.esize
+                v["dst_len"] = p.metas["dst_len"]
+                v["nv"] = p.metas["nv"]
+                v["kind"] = dc.esize if dc.kind == "plain" else _PQK_CODES
+                v["flags"] = p.metas["flags"] & _PQF_HAS_DEF
+                if dc.kind == "dict":
+                    v["code_lim"] = len(p.dict_vals)
+                    if lut is not None:
+                        v["lut"] = blob.data_ptr() + la
+                        host[la:la + lut.nbytes] = lut.view(np.uint8)
+                at += p.n_pages
+            _TABLES.upload(host, blob)
+            K.pq_decompress_multi(blob[:dec_bytes], n_dec)
+            if n_val:
+                K.pq_values_multi(blob[dec_bytes:dec_bytes + val_bytes],
+                                  n_val, err)
         for e in group:
-            if e[5] is None:
+            if e[3] is None:
                 continue
-            reader, field = e[3], e[4]
+            if e[5] is not None:  # written in place by pq_values_multi
+                e[3] = None
+                STATS["batched"] += 1
+                STATS["direct"] += 1
+                continue
+            reader, field = e[1], e[2]
             try:
-                col = reader._finish_batched(e[5], device, field)
+                col = reader._finish_batched(e[3], device, field)
             except Exception:
                 col = None
-            e[5] = None  # drop the chunk's source and scratch tensors
+            e[3] = None  # drop the chunk's source and scratch tensors
             if col is not None:
                 STATS["batched"] += 1
             else:  # today's per-chunk route, from the top
                 col = reader.decode_column(device, field)
-            e[6] = col
+            e[4] = col
         if preps:
             done = torch.cuda.Event()
             done.record()
             inflight.append((done, len(preps)))
         STATS["t_decode"] = STATS.get("t_decode", 0.0) + \
             time.perf_counter() - t0
-        ok = all(e[6] is not None for e in group)
-        cur_cols: List[Column] = []
-        cur_names: List[str] = []
-        rg_names = None
+        ok = True
         for e in group:
-            if e[2] and cur_cols:
-                rg_tables.append(Table(cur_names, cur_cols).select(
-                    [n for n in rg_names if n in cur_names]))
-                cur_cols, cur_names = [], []
-            rg_names = e[1]
-            cur_cols.append(e[6])
-            cur_names.append(e[0])
-        if ok and cur_cols:
-            rg_tables.append(Table(cur_names, cur_cols).select(
-                [n for n in rg_names if n in cur_names]))
+            if e[5] is not None:
+                continue
+            if e[4] is None:
+                ok = False
+                break
+            pieces.setdefault(e[0], []).append(e[4])
         group, group_rgs = [], 0
         return ok
 
+    names = items[0][7]
     try:
         futs = [ex.submit(fetch, k) for k in range(len(items))]
         for k, fut in enumerate(futs):
-            fp, rg, cm, field, start, size, first, names = items[k]
+            fp, rg, cm, field, start, size, first, names, row0, nrows = \
+                items[k]
             if first:
                 if group_rgs >= _GROUP_ROW_GROUPS and not flush():
                     return None
@@ -820,17 +1098,34 @@ def _read_pieces_pipelined(my, columns, ctx) -> Optional[Table]:
             ev = torch.cuda.Event()
             ev.record()
             s["ev"] = ev
-            sems[i].release()
+            with gate:
+                released[0] = k + 1
+                gate.notify_all()
+            name = cm.path_in_schema
+            dc = plan.get(name)
             reader = _ChunkReader(
                 None, cm, cm.physical_type,
                 max_def=1 if field.nullable else 0,
                 prefetched=(hdrs, dev, dict_raw, (fp, start, size)))
             try:
-                prep = reader._prepare_batched(device)
+                prep = reader._prepare_batched(device,
+                                               upload_metas=dc is None)
             except Exception:
                 prep = None
             col = None
-            if prep is None:
+            dinfo = None
+            if dc is not None:
+                # the pages must be what the footer promised
+                if (prep is None or prep.mode != dc.kind
+                        or prep.total_nv != nrows
+                        or (dc.kind == "dict" and (
+                            prep.dict_vals is None
+                            or prep.dict_vals.dtype != object))):
+                    return _RETRY
+                lut = dc.unifier.add(prep.dict_vals) \
+                    if dc.kind == "dict" else None
+                dinfo = (dc, row0, lut)
+            elif prep is None:
                 # not eligible for the batched path: the per-chunk route
                 # now, so the chunk does not hold up its group
                 col = reader.decode_column(device, field)
@@ -841,17 +1136,37 @@ def _read_pieces_pipelined(my, columns, ctx) -> Optional[Table]:
                 time.perf_counter() - t0
             if prep is None and col is None:
                 return None
-            group.append([cm.path_in_schema, names, first, reader, field,
-                          prep, col])
+            if name not in metas_of:
+                seen_names.append(name)
+                field_of[name] = field
+            metas_of.setdefault(name, []).append(cm)
+            group.append([name, reader, field, prep, col, dinfo])
         if not flush():
             return None
     finally:
-        ex.shutdown(wait=True)
-    if len(rg_tables) == 1:
-        return rg_tables[0]
-    from .. import ops
-
-    return ops.concat_tables(rg_tables)
+        with gate:
+            stop[0] = True
+            gate.notify_all()
+        ex.shutdown(wait=True, cancel_futures=True)
+    if err is not None and int(err.item()) != 0:  # the read's one sync
+        return _RETRY
+    out_names = [n for n in names if n in seen_names]
+    out_cols = []
+    for n in out_names:
+        dc = plan.get(n)
+        if dc is None:
+            col = ops.concat_columns(pieces[n])
+        elif dc.kind == "dict":
+            col = Column(bt.dictionary, dc.data,
+                         dictionary=dc.unifier.dictionary(),
+                         length=total_rows)
+        else:
+            col = _fixed_column(dc.data, dc.field.type)
+        vr = _val_range_from_meta(metas_of[n], field_of[n].type)
+        if vr is not None:
+            col.val_range = vr
+        out_cols.append(col)
+    return Table(out_names, out_cols, total_rows)
 
 
 def _read_row_group_gpu(fp: str, rg: int, columns, ctx) -> Optional[Table]:

@@ -1294,6 +1294,9 @@ def udf_map(a: Column, func, na_action=None) -> Column:
 
                 vals = [func(v) for v in range(lo, hi + 1)]
                 pos = (a.data.long() - lo)
+                if a.mask is not None:
+                    # null slots hold filler that val_range does not cover
+                    pos = pos.clamp_(0, hi - lo)
                 if all(isinstance(v, str) for v in vals):
                     udict, inv = np.unique(np.array(vals, dtype=object),
                                            return_inverse=True)

@@ -1126,6 +1126,8 @@ torch::Tensor gemm_f32(torch::Tensor A, torch::Tensor B);  // gemm.hip
 void pq_decompress(torch::Tensor src, torch::Tensor pages_blob,
                    int64_t n_pages, torch::Tensor scratch);
 void pq_decompress_multi(torch::Tensor pages_blob, int64_t n_pages);
+void pq_values_multi(torch::Tensor pages_blob, int64_t n_pages,
+                     torch::Tensor err);
 std::vector<torch::Tensor> pq_def_levels(torch::Tensor scratch,
                                          torch::Tensor pages_blob,
                                          int64_t n_pages, int64_t bitwidth,
@@ -1176,6 +1178,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "page-parallel snappy decompress (one wave/page)");
   m.def("pq_decompress_multi", &pq_decompress_multi,
         "snappy decompress over a table of absolute page addresses");
+  m.def("pq_values_multi", &pq_values_multi,
+        "checked PLAIN / dictionary-code pages of a group -> shard columns");
   m.def("pq_def_levels", &pq_def_levels,
         "definition levels -> validity mask + per-page valid counts");
   m.def("pq_expand_codes", &pq_expand_codes,

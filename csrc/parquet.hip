@@ -10,7 +10,9 @@
 // pages of about 160 KB for a 2^23-row int64 chunk of the flagship shard);
 // pq_decompress_multi takes a table of absolute page addresses, so the
 // pipelined shard reader decompresses every column chunk of a group of row
-// groups in one launch (about 2100 pages per row group of that shard).
+// groups in one launch (about 2100 pages per row group of that shard), and
+// pq_values_multi then writes the values of the group's null-free chunks
+// straight into the shard's columns.
 //
 // Also hosts the C++ (host-side) page-header parser: a minimal Thrift
 // compact-protocol walk over the chunk buffer, returning a page table as
@@ -468,6 +470,103 @@ __global__ void pq_def_levels_kernel(const uint8_t* __restrict__ scratch,
 // RLE/bit-packed dictionary codes -> dense int32 codes
 // ---------------------------------------------------------------------
 
+// varint of at most 5 bytes inside b[*pos, end); false when it runs out
+DEV_INLINE bool pq_varint32(const uint8_t* b, int64_t* pos, int64_t end,
+                            int64_t* out) {
+  int64_t v = 0;
+  for (int shift = 0; shift < 35; shift += 7) {
+    if (*pos >= end) return false;
+    uint8_t c = b[*pos];
+    (*pos)++;
+    v |= (int64_t)(c & 0x7F) << shift;
+    if (!(c & 0x80)) {
+      *out = v;
+      return true;
+    }
+  }
+  return false;
+}
+
+#define PQ_CODES_OK 0
+#define PQ_CODES_STREAM 1  // bit width or run structure, or fewer than nval
+#define PQ_CODES_RANGE 2   // a code at or above code_lim (not stored)
+
+// One wave expands the codes section of one page: base points at the
+// bit-width byte, dlen bytes are the page's from there on, nval codes go
+// to o[0, nval).  A code c is stored as lut[c] when lut is set and is
+// dropped, with PQ_CODES_RANGE returned, unless (uint32_t)c < code_lim.
+// A bit-packed value may be read as a 4-byte word that ends up to 3 bytes
+// past its run: the page tables keep pages inside padded scratch.
+DEV_INLINE int pq_expand_codes_page(const uint8_t* base, int64_t dlen,
+                                    int64_t nval, int32_t* __restrict__ o,
+                                    const int32_t* __restrict__ lut,
+                                    uint32_t code_lim, int lane) {
+  if (dlen < 1) return nval ? PQ_CODES_STREAM : PQ_CODES_OK;
+  int bitwidth = base[0];
+  const uint8_t* d = base + 1;
+  dlen -= 1;
+  int st = PQ_CODES_OK;
+  if (bitwidth == 0) {
+    if (!nval) return PQ_CODES_OK;
+    if (!code_lim) return PQ_CODES_RANGE;
+    int32_t v = lut ? lut[0] : 0;
+    for (int64_t i = lane; i < nval; i += WAVE) o[i] = v;
+    return PQ_CODES_OK;
+  }
+  if (bitwidth > 24) return PQ_CODES_STREAM;
+  int width_bytes = (bitwidth + 7) / 8;
+  int64_t pos = 0, outp = 0;
+  int oob = 0;
+  while (outp < nval && pos < dlen) {
+    int64_t h = 0, val = 0, count;
+    int okh = 1;
+    if (lane == 0) okh = pq_varint32(d, &pos, dlen, &h);
+    if (!__shfl(okh, 0)) break;
+    h = __shfl(h, 0);
+    pos = __shfl(pos, 0);
+    if (h & 1) {
+      int64_t groups = h >> 1;
+      if (pos + groups * bitwidth > dlen) break;
+      count = groups * 8;
+      if (count > nval - outp) count = nval - outp;
+      int64_t bitoff = pos * 8;
+      for (int64_t i = lane; i < count; i += WAVE) {
+        int64_t bp = bitoff + i * bitwidth;
+        int64_t byte = bp >> 3;
+        uint32_t w = (uint32_t)d[byte] | ((uint32_t)d[byte + 1] << 8) |
+                     ((uint32_t)d[byte + 2] << 16) |
+                     ((uint32_t)d[byte + 3] << 24);
+        uint32_t c = (w >> (bp & 7)) & ((1u << bitwidth) - 1);
+        if (c < code_lim) o[outp + i] = lut ? lut[c] : (int32_t)c;
+        else oob = 1;
+      }
+      pos += groups * bitwidth;
+    } else {
+      count = h >> 1;
+      if (count > nval - outp) count = nval - outp;
+      if (pos + width_bytes > dlen) break;
+      if (lane == 0) {
+        val = 0;
+        for (int i = 0; i < width_bytes; ++i)
+          val |= (int64_t)d[pos + i] << (8 * i);
+      }
+      pos += width_bytes;
+      val = __shfl(val, 0);
+      uint32_t c = (uint32_t)val;
+      if (c < code_lim) {
+        int32_t v = lut ? lut[c] : (int32_t)c;
+        for (int64_t i = lane; i < count; i += WAVE) o[outp + i] = v;
+      } else if (count) {
+        oob = 1;
+      }
+    }
+    outp += count;
+  }
+  if (outp < nval) st |= PQ_CODES_STREAM;
+  if (__ballot(oob)) st |= PQ_CODES_RANGE;
+  return st;
+}
+
 __global__ void pq_expand_codes_kernel(const uint8_t* __restrict__ scratch,
                                        const PageMeta* __restrict__ pages,
                                        int n_pages,
@@ -480,54 +579,11 @@ __global__ void pq_expand_codes_kernel(const uint8_t* __restrict__ scratch,
   int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) / WAVE;
   for (int64_t p = wave; p < n_pages; p += n_waves) {
     PageMeta pm = pages[p];
-    const uint8_t* base = scratch + pm.dst_off +
-                          (val_data_off ? val_data_off[p] : 0);
-    int32_t* o = out + dense_off[p];
+    int64_t voff = val_data_off ? val_data_off[p] : 0;
     int64_t nval = n_valid ? (int64_t)n_valid[p] : (int64_t)pm.nv;
-    int bitwidth = base[0];
-    const uint8_t* d = base + 1;
-    if (bitwidth == 0) {
-      for (int64_t i = lane; i < nval; i += WAVE) o[i] = 0;
-      continue;
-    }
-    int width_bytes = (bitwidth + 7) / 8;
-    int64_t pos = 0, outp = 0;
-    int64_t dlen = pm.dst_len - (base - (scratch + pm.dst_off));
-    while (outp < nval && pos < dlen) {
-      int64_t h = 0, val = 0, count;
-      if (lane == 0) h = dev_varint(d, &pos);
-      h = __shfl(h, 0);
-      if (h & 1) {
-        int64_t groups = h >> 1;
-        count = groups * 8;
-        if (count > nval - outp) count = nval - outp;
-        int64_t bitoff = __shfl(pos, 0) * 8;
-        for (int64_t i = lane; i < count; i += WAVE) {
-          int64_t bp = bitoff + i * bitwidth;
-          int64_t byte = bp >> 3;
-          uint32_t w = (uint32_t)d[byte] | ((uint32_t)d[byte + 1] << 8) |
-                       ((uint32_t)d[byte + 2] << 16) |
-                       ((uint32_t)d[byte + 3] << 24);
-          o[outp + i] = (int32_t)((w >> (bp & 7)) & ((1u << bitwidth) - 1));
-        }
-        if (lane == 0) pos += groups * bitwidth;
-        pos = __shfl(pos, 0);
-      } else {
-        count = h >> 1;
-        if (count > nval - outp) count = nval - outp;
-        if (lane == 0) {
-          val = 0;
-          for (int i = 0; i < width_bytes; ++i)
-            val |= (int64_t)d[pos + i] << (8 * i);
-          pos += width_bytes;
-        }
-        val = __shfl(val, 0);
-        pos = __shfl(pos, 0);
-        int32_t v = (int32_t)val;
-        for (int64_t i = lane; i < count; i += WAVE) o[outp + i] = v;
-      }
-      outp += count;
-    }
+    // codes are not range-checked here: the dictionary lives on the host
+    pq_expand_codes_page(scratch + pm.dst_off + voff, pm.dst_len - voff, nval,
+                         out + dense_off[p], nullptr, 0xFFFFFFFFu, lane);
   }
 }
 
@@ -536,6 +592,46 @@ __global__ void pq_expand_codes_kernel(const uint8_t* __restrict__ scratch,
 // unaligned inside the decompressed page, destination is esize-aligned)
 // ---------------------------------------------------------------------
 
+// nthreads threads (tid of them this one) copy nbytes from s, at any byte
+// address inside a decompressed page, to o, which is 8-byte aligned or, for
+// 4-byte elements, 4-byte aligned.  Loads are aligned u64 words merged by
+// a shift; the word after the last one needed may be read too, at most 15
+// bytes past s + nbytes, which the 16 bytes of scratch padding cover.
+// Stores: with o 8-byte aligned, nbytes / 8 words and then the bytes
+// [8 * (nbytes / 8), nbytes); otherwise nbytes / 4 words and then the bytes
+// [4 * (nbytes / 4), nbytes).  Either way the last byte stored is
+// o[nbytes - 1], so the destination needs no padding.
+DEV_INLINE void pq_copy_fixed_page(const uint8_t* __restrict__ s,
+                                   uint8_t* __restrict__ o, int64_t nbytes,
+                                   int tid, int nthreads) {
+  int m = (int)((uintptr_t)s & 7);
+  const uint64_t* sa = (const uint64_t*)(s - m);
+  int sh = m * 8;
+  if ((((uintptr_t)o) & 7) == 0) {
+    int64_t nw = nbytes / 8;
+    if (sh == 0) {
+      for (int64_t i = tid; i < nw; i += nthreads) ((uint64_t*)o)[i] = sa[i];
+    } else {
+      for (int64_t i = tid; i < nw; i += nthreads)
+        ((uint64_t*)o)[i] = (sa[i] >> sh) | (sa[i + 1] << (64 - sh));
+    }
+    for (int64_t i = nw * 8 + tid; i < nbytes; i += nthreads) o[i] = s[i];
+  } else {  // esize 4 destination at 4-byte alignment
+    int64_t nw = nbytes / 4;
+    for (int64_t i = tid; i < nw; i += nthreads) {
+      int64_t bit = (int64_t)i * 32 + sh;
+      uint64_t w = sa[bit >> 6];
+      int off = (int)(bit & 63);
+      uint32_t v = (off <= 32)
+                       ? (uint32_t)(w >> off)
+                       : (uint32_t)((w >> off) |
+                                    (sa[(bit >> 6) + 1] << (64 - off)));
+      ((uint32_t*)o)[i] = v;
+    }
+    for (int64_t i = nw * 4 + tid; i < nbytes; i += nthreads) o[i] = s[i];
+  }
+}
+
 __global__ void pq_copy_fixed_kernel(const uint8_t* __restrict__ scratch,
                                      const PageMeta* __restrict__ pages,
                                      int n_pages,
@@ -543,45 +639,132 @@ __global__ void pq_copy_fixed_kernel(const uint8_t* __restrict__ scratch,
                                      const int64_t* __restrict__ dense_off,
                                      const int32_t* __restrict__ n_valid,
                                      int esize, uint8_t* __restrict__ out) {
-  // one BLOCK per page slot (pages are up to ~1 MiB: need more than a wave).
-  // Source is byte-misaligned inside the decompressed page; do shift-merged
-  // aligned u64 loads (scratch is padded by 16 bytes so the +1 word read
-  // never faults) and aligned stores sized to the destination alignment.
+  // one BLOCK per page slot (pages are up to ~1 MiB: need more than a wave)
   for (int64_t p = blockIdx.x; p < n_pages; p += gridDim.x) {
     PageMeta pm = pages[p];
     const uint8_t* s = scratch + pm.dst_off +
                        (val_data_off ? val_data_off[p] : 0);
     uint8_t* o = out + dense_off[p] * esize;
     int64_t nbytes = (n_valid ? (int64_t)n_valid[p] : (int64_t)pm.nv) * esize;
-    int m = (int)((uintptr_t)s & 7);
-    const uint64_t* sa = (const uint64_t*)(s - m);
-    int sh = m * 8;
-    if ((((uintptr_t)o) & 7) == 0) {
-      int64_t nw = nbytes / 8;
-      if (sh == 0) {
-        for (int64_t i = threadIdx.x; i < nw; i += blockDim.x)
-          ((uint64_t*)o)[i] = sa[i];
+    pq_copy_fixed_page(s, o, nbytes, threadIdx.x, blockDim.x);
+  }
+}
+
+// ---------------------------------------------------------------------
+// Values of a whole group of row groups, decoded in place: a table of
+// pages of many column chunks, each with the absolute address in the final
+// shard column where its first value goes.  These chunks hold no nulls, by
+// their statistics, so a page's definition levels are only checked: they
+// must cover nv values, all of them 1.  A page that fails a check is left
+// unwritten and its reason is ORed into *err; the reader then decodes the
+// shard again on the per-chunk route.
+// ---------------------------------------------------------------------
+
+struct ValPage {  // page table entry of pq_values_multi
+  const uint8_t* page;  // decompressed page (PagePtr::dst)
+  uint8_t* out;         // where this page's first value goes
+  const int32_t* lut;   // codes: code -> unified code, or null
+  int32_t dst_len;      // decompressed page length
+  int32_t nv;           // values in the page
+  int32_t kind;         // PQK_CODES, or the element size of PLAIN: 4 or 8
+  int32_t flags;        // PQF_HAS_DEF
+  int32_t code_lim;     // codes: entries of lut, or of the dictionary
+  int32_t pad;
+};
+
+#define PQK_CODES 0
+
+#define PQE_PREFIX 1  // level section or PLAIN values do not fit the page
+#define PQE_LEVELS 2  // levels malformed, short of nv, or not all 1
+#define PQE_ENTRY 4   // table entry: kind, alignment, negative counts
+#define PQE_CODES 8   // code stream malformed or short of nv
+#define PQE_RANGE 16  // dictionary code outside the LUT / dictionary
+
+// The block checks the level prefix of one page and returns 0 with *voff =
+// offset of the values section, or PQE_* bits.  Run headers are parsed by
+// every thread alike (a few bytes for RLE runs); the bytes of bit-packed
+// runs are spread over the threads.  Every thread of the block calls this.
+DEV_INLINE int pq_check_levels(const uint8_t* __restrict__ page, int dst_len,
+                               int nv, int tid, int nthreads, int* voff) {
+  int bad = 0, mine = 0;
+  int64_t lvl_len = 0;
+  if (dst_len < 4) {
+    bad = PQE_PREFIX;
+  } else {
+    lvl_len = (int32_t)((uint32_t)page[0] | ((uint32_t)page[1] << 8) |
+                        ((uint32_t)page[2] << 16) | ((uint32_t)page[3] << 24));
+    if (lvl_len < 0 || 4 + lvl_len > dst_len) bad = PQE_PREFIX;
+  }
+  if (!bad) {
+    const uint8_t* lv = page + 4;
+    int64_t pos = 0, out = 0;
+    while (out < nv && pos < lvl_len) {
+      int64_t h;
+      if (!pq_varint32(lv, &pos, lvl_len, &h)) break;
+      int64_t count;
+      if (h & 1) {  // bit-packed, 1 bit per level: groups bytes
+        int64_t groups = h >> 1;
+        if (pos + groups > lvl_len) break;
+        count = groups * 8;
+        if (count > nv - out) count = nv - out;
+        int64_t full = count >> 3;
+        for (int64_t i = tid; i < full; i += nthreads)
+          if (lv[pos + i] != 0xFF) mine = PQE_LEVELS;
+        int rest = (int)(count & 7);
+        if (rest && (lv[pos + full] & ((1 << rest) - 1)) != (1 << rest) - 1)
+          bad = PQE_LEVELS;
+        pos += groups;
       } else {
-        for (int64_t i = threadIdx.x; i < nw; i += blockDim.x)
-          ((uint64_t*)o)[i] = (sa[i] >> sh) | (sa[i + 1] << (64 - sh));
+        count = h >> 1;
+        if (count > nv - out) count = nv - out;
+        if (pos >= lvl_len) break;
+        if (count && lv[pos] != 1) bad = PQE_LEVELS;
+        pos += 1;
       }
-      for (int64_t i = nw * 8 + threadIdx.x; i < nbytes; i += blockDim.x)
-        o[i] = s[i];
-    } else {  // esize 4 destination at 4-byte alignment
-      int64_t nw = nbytes / 4;
-      for (int64_t i = threadIdx.x; i < nw; i += blockDim.x) {
-        int64_t bit = (int64_t)i * 32 + sh;
-        uint64_t w = sa[bit >> 6];
-        int off = (int)(bit & 63);
-        uint32_t v = (off <= 32)
-                         ? (uint32_t)(w >> off)
-                         : (uint32_t)((w >> off) |
-                                      (sa[(bit >> 6) + 1] << (64 - off)));
-        ((uint32_t*)o)[i] = v;
-      }
-      for (int64_t i = nw * 4 + threadIdx.x; i < nbytes; i += blockDim.x)
-        o[i] = s[i];
+      out += count;
     }
+    if (out != nv) bad |= PQE_LEVELS;
+  }
+  if (__syncthreads_or(mine)) bad |= PQE_LEVELS;
+  *voff = 4 + (int)lvl_len;
+  return bad;
+}
+
+// KIND_CODES false: one block per PLAIN page; true: one wave (= block) per
+// codes page.  Entries of the other kind are skipped.
+template <bool KIND_CODES>
+__global__ void pq_values_multi_kernel(const ValPage* __restrict__ pages,
+                                       int n_pages, int32_t* err) {
+  for (int p = blockIdx.x; p < n_pages; p += gridDim.x) {
+    ValPage e = pages[p];
+    if ((e.kind == PQK_CODES) != KIND_CODES) continue;
+    int bad = 0, voff = 0;
+    if (e.dst_len < 0 || e.nv < 0) bad = PQE_ENTRY;
+    if (!KIND_CODES) {
+      if (e.kind != 4 && e.kind != 8) bad = PQE_ENTRY;
+      else if ((uintptr_t)e.out & 3) bad = PQE_ENTRY;
+      else if (e.kind == 8 && ((uintptr_t)e.out & 7)) bad = PQE_ENTRY;
+    } else if ((uintptr_t)e.out & 3) {
+      bad = PQE_ENTRY;
+    }
+    if (!bad && (e.flags & PQF_HAS_DEF))
+      bad = pq_check_levels(e.page, e.dst_len, e.nv, threadIdx.x, blockDim.x,
+                            &voff);
+    if (!bad) {
+      if (!KIND_CODES) {
+        int64_t nbytes = (int64_t)e.nv * e.kind;
+        if (voff + nbytes > e.dst_len) bad = PQE_PREFIX;
+        else pq_copy_fixed_page(e.page + voff, e.out, nbytes, threadIdx.x,
+                                blockDim.x);
+      } else {
+        int st = pq_expand_codes_page(
+            e.page + voff, (int64_t)e.dst_len - voff, e.nv, (int32_t*)e.out,
+            e.lut, (uint32_t)(e.code_lim < 0 ? 0 : e.code_lim), threadIdx.x);
+        if (st & PQ_CODES_STREAM) bad |= PQE_CODES;
+        if (st & PQ_CODES_RANGE) bad |= PQE_RANGE;
+      }
+    }
+    if (bad && threadIdx.x == 0) atomicOr(err, bad);
   }
 }
 
@@ -671,6 +854,31 @@ void pq_decompress_multi(torch::Tensor pages_blob, int64_t n_pages) {
   hipLaunchKernelGGL(pq_decompress_multi_kernel,
                      dim3(pq_grid_pages(n_pages)), dim3(WAVE), 0, pq_stream(),
                      (const PagePtr*)pages_blob.data_ptr(), (int)n_pages);
+  CHECK_HIP_PQ(hipGetLastError());
+}
+
+// pages_blob: device bytes of n_pages ValPage entries; err: one int32 on
+// the device, ORed into.  Two launches whatever the table holds: PLAIN
+// pages one block each, codes pages one wave each.
+void pq_values_multi(torch::Tensor pages_blob, int64_t n_pages,
+                     torch::Tensor err) {
+  if (!n_pages) return;
+  TORCH_CHECK(pages_blob.is_contiguous() &&
+                  pages_blob.numel() * pages_blob.element_size() >=
+                      n_pages * (int64_t)sizeof(ValPage),
+              "pq_values_multi: page table too small");
+  TORCH_CHECK(n_pages < (1ll << 31), "pq_values_multi: too many pages");
+  TORCH_CHECK(err.scalar_type() == torch::kInt32 && err.numel() >= 1 &&
+                  err.device() == pages_blob.device(),
+              "pq_values_multi: err must be an int32 on the table's device");
+  int grid = (int)std::min<int64_t>(n_pages, 1 << 16);
+  hipLaunchKernelGGL(pq_values_multi_kernel<false>, dim3(grid), dim3(256), 0,
+                     pq_stream(), (const ValPage*)pages_blob.data_ptr(),
+                     (int)n_pages, (int32_t*)err.data_ptr());
+  CHECK_HIP_PQ(hipGetLastError());
+  hipLaunchKernelGGL(pq_values_multi_kernel<true>, dim3(grid), dim3(WAVE), 0,
+                     pq_stream(), (const ValPage*)pages_blob.data_ptr(),
+                     (int)n_pages, (int32_t*)err.data_ptr());
   CHECK_HIP_PQ(hipGetLastError());
 }
 

@@ -1,0 +1,253 @@
+"""In-place shard decode: eligible chunks are written by one
+pq_values_multi call per group straight into whole-shard columns; the rest
+keep the per-chunk finish.  Two snappy files of three row groups (4999,
+5000, 5001 rows), so the second row group's 4-byte columns start at an
+address that is 4- but not 8-byte aligned, and 4 KiB pages whose values
+start at odd offsets behind the definition-level prefix."""
+
+import numpy as np
+import pandas as pd
+import pyarrow as pa
+import pyarrow.parquet as pq
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+RG_ROWS = (4999, 5000, 5001)
+N_FILES = 2
+WORDS = ["alpha", "beta", "gamma", "delta"]
+# columns decoded in place / columns that keep the per-chunk finish
+DIRECT_COLS = ["loc", "f", "i32", "f32", "ts", "req", "s_dict", "cat"]
+OTHER_COLS = ["nul", "s_plain", "nostat"]
+SCHEMA = pa.schema([
+    pa.field("loc", pa.int64()),
+    pa.field("f", pa.float64()),
+    pa.field("i32", pa.int32()),
+    pa.field("f32", pa.float32()),
+    pa.field("ts", pa.timestamp("us")),
+    pa.field("req", pa.int64(), nullable=False),
+    pa.field("s_dict", pa.string()),
+    pa.field("nul", pa.int64()),
+    pa.field("s_plain", pa.string()),
+    pa.field("nostat", pa.int64()),
+    # a dictionary array, as a table written from dictionary columns has it
+    pa.field("cat", pa.dictionary(pa.int32(), pa.large_string())),
+])
+
+
+def _row_group(rng, n, k):
+    # every row group meets the words in another first order; the fourth
+    # one never sees "delta"
+    words = WORDS[k % 4:] + WORDS[:k % 4]
+    if k == 3:
+        words = [w for w in words if w != "delta"]
+    s_dict = np.concatenate([words, rng.choice(words, n - len(words))])
+    return pa.table({
+        "loc": rng.integers(1, 266, n).astype("int64"),
+        "f": rng.random(n),
+        "i32": rng.integers(-10**6, 10**6, n).astype("int32"),
+        "f32": rng.random(n).astype("float32"),
+        "ts": pa.array(rng.integers(0, 2 * 10**15, n),
+                       type=pa.timestamp("us")),
+        "req": rng.integers(-10**12, 10**12, n).astype("int64"),
+        "s_dict": pa.array(s_dict.tolist(), type=pa.string()),
+        "nul": pa.array(rng.integers(-10**12, 10**12, n), type=pa.int64(),
+                        mask=rng.random(n) < 0.10),
+        "s_plain": pa.array(["s" + str(v)
+                             for v in rng.integers(0, 10**9, n)]),
+        "nostat": rng.integers(0, 1000, n).astype("int64"),
+        "cat": pa.DictionaryArray.from_arrays(
+            pa.array(rng.integers(0, 3, n).astype(np.int32)),
+            pa.array(["HV3", "HV4", "HV5"], type=pa.large_string())),
+    }, schema=SCHEMA)
+
+
+@pytest.fixture(scope="module")
+def shard(tmp_path_factory):
+    d = tmp_path_factory.mktemp("direct")
+    rng = np.random.default_rng(99)
+    k = 0
+    for i in range(N_FILES):
+        path = str(d / f"part-{i:05d}.parquet")
+        with pq.ParquetWriter(
+                path, SCHEMA, compression="SNAPPY",
+                use_dictionary=["s_dict", "cat"], data_page_size=4096,
+                write_statistics=[c for c in SCHEMA.names
+                                  if c != "nostat"]) as w:
+            for n in RG_ROWS:
+                w.write_table(_row_group(rng, n, k), row_group_size=n)
+                k += 1
+        md = pq.ParquetFile(path).metadata
+        assert [md.row_group(r).num_rows
+                for r in range(md.num_row_groups)] == list(RG_ROWS)
+    ref = pa.concat_tables(
+        [pq.read_table(str(d / f"part-{i:05d}.parquet"))
+         for i in range(N_FILES)])
+    return str(d), ref
+
+
+@pytest.mark.parametrize("group", [None, 1, 2, 4],
+                         ids=["default", "g1", "g2", "g4"])
+def test_direct_decode_matches_pyarrow(shard, group, monkeypatch):
+    from bodo_amd.engine.executor import ExecutionContext
+    from bodo_amd.io import parquet_gpu as g
+
+    path, ref_tbl = shard
+    ref = ref_tbl.to_pandas()
+    if group is not None:
+        monkeypatch.setattr(g, "_GROUP_ROW_GROUPS", group)
+    assert g.DIRECT
+    ctx = ExecutionContext("cuda")
+    ctx.world, ctx.rank = 1, 0
+    before = dict(g.STATS)
+    t = g.read_shard_gpu(path, None, ctx)
+    assert t is not None, "GPU decode fell back"
+    n_rgs = N_FILES * len(RG_ROWS)
+    assert g.STATS["slow"] == before["slow"]
+    assert g.STATS["direct"] == before["direct"] + n_rgs * len(DIRECT_COLS)
+    assert g.STATS["batched"] == before["batched"] + n_rgs * len(SCHEMA.names)
+
+    # the dictionary column: unified in first-seen order, one code space
+    sd = t.column("s_dict")
+    assert sd.dictionary.to_pylist() == ["alpha", "beta", "gamma", "delta"]
+    assert len(sd) == len(ref) and sd.mask is None
+
+    # val_range from the footer: integer columns with statistics only
+    for c in ("loc", "i32", "req"):
+        v = ref[c].to_numpy()
+        assert t.column(c).val_range == (int(v.min()), int(v.max())), c
+    nul = ref["nul"].dropna().to_numpy()
+    assert t.column("nul").val_range == (int(nul.min()), int(nul.max()))
+    for c in ("nostat", "f", "f32", "ts", "s_dict", "s_plain", "cat"):
+        assert t.column(c).val_range is None, c
+    assert t.column("nul").mask is not None
+    for c in DIRECT_COLS + ["nostat"]:
+        assert t.column(c).mask is None, c
+
+    out = t.to_pandas()
+    for c in out.columns:
+        if out[c].dtype.name == "category":
+            out[c] = out[c].astype(object)
+    assert list(out.columns) == list(ref.columns)
+    assert len(out) == len(ref) == N_FILES * sum(RG_ROWS)
+    for c in ref.columns:
+        a, b = out[c], ref[c]
+        assert (a.isna().to_numpy() == b.isna().to_numpy()).all(), c
+        ok = ~b.isna().to_numpy()
+        assert (a.to_numpy()[ok] == b.to_numpy()[ok]).all(), c
+    assert int(ref["nul"].isna().sum()) > 0
+
+
+def test_direct_off_gives_the_same_table(shard, monkeypatch):
+    """The route the reader falls back to: no chunk decoded in place."""
+    from bodo_amd.engine.executor import ExecutionContext
+    from bodo_amd.io import parquet_gpu as g
+
+    path, ref_tbl = shard
+    ctx = ExecutionContext("cuda")
+    ctx.world, ctx.rank = 1, 0
+    on = g.read_shard_gpu(path, None, ctx)
+    monkeypatch.setattr(g, "DIRECT", False)
+    before = dict(g.STATS)
+    off = g.read_shard_gpu(path, None, ctx)
+    assert g.STATS["direct"] == before["direct"]
+    assert on.names == off.names
+    for name in on.names:
+        a, b = on.column(name), off.column(name)
+        assert a.val_range == b.val_range, name
+        assert a.dtype.kind == b.dtype.kind, name
+        if a.dictionary is not None:
+            assert a.dictionary.to_pylist() == b.dictionary.to_pylist()
+        if a.offsets is not None:
+            assert bool((a.offsets == b.offsets).all()), name
+        assert a.data.dtype == b.data.dtype, name
+        assert bool((a.data.view(dtype=_bits(a.data)) ==
+                     b.data.view(dtype=_bits(b.data))).all()), name
+        assert (a.mask is None) == (b.mask is None), name
+        if a.mask is not None:
+            assert bool((a.mask == b.mask).all()), name
+
+
+def _bits(t):
+    import torch
+
+    return {1: torch.uint8, 4: torch.int32, 8: torch.int64}[t.element_size()]
+
+
+def _page(levels: bytes, lvl_len, body: bytes) -> bytes:
+    return np.int32(lvl_len).tobytes() + levels + body
+
+
+def test_values_multi_guards_bad_pages():
+    """Pages whose definition levels are not all 1, or whose level section
+    overruns the page, are reported through err and not written; a good
+    page of the same launch is copied."""
+    import bodo_amd_kernels as K
+    import torch
+
+    from bodo_amd.io import parquet_gpu as g
+
+    rng = np.random.default_rng(3)
+    nv_a = nv_b = 8
+    nv_c, nv_d = 300, 10
+    vals_a = rng.integers(1, 10**9, nv_a).astype(np.int64)
+    vals_c = rng.integers(-10**15, 10**15, nv_c).astype(np.int64)
+    # A: one bit-packed group of 8 levels with a 0 in it
+    page_a = _page(bytes([3, 0b11110111]), 2, vals_a.tobytes())
+    # B: level section longer than the page
+    page_b = _page(bytes([16, 1]), 1000, vals_a.tobytes())
+    # C: well formed; an RLE run of 300 ones (2-byte header), values at +7
+    page_c = _page(bytes([0xD8, 0x04, 1]), 3, vals_c.tobytes())
+    # D: well-formed levels, dictionary code 3 against a 2-entry table
+    page_d = _page(bytes([nv_d << 1, 1]), 2, bytes([2, nv_d << 1, 3]))
+    pages = [page_a, page_b, page_c, page_d]
+    offs, at = [], 0
+    for p in pages:
+        offs.append(at)
+        at += (len(p) + 7) & ~7
+    scratch_np = np.zeros(at + 16, dtype=np.uint8)  # the reader's padding
+    for o, p in zip(offs, pages):
+        scratch_np[o:o + len(p)] = np.frombuffer(p, dtype=np.uint8)
+    dev = "cuda"
+    scratch = torch.from_numpy(scratch_np).to(dev)
+
+    guard = 4
+    sentinel = 0x5A5A5A5A5A5A5A5A
+    n_out = guard + nv_a + nv_b + nv_c + guard
+    out = torch.full((n_out,), sentinel, dtype=torch.int64, device=dev)
+    codes = torch.full((guard + nv_d + guard,), 0x5A5A5A5A,
+                       dtype=torch.int32, device=dev)
+    lut = torch.tensor([7, 9], dtype=torch.int32, device=dev)
+    tbl = np.zeros(4, dtype=g._VALPAGE_DT)
+    tbl["page"] = [scratch.data_ptr() + o for o in offs]
+    tbl["out"] = [out.data_ptr() + 8 * guard,
+                  out.data_ptr() + 8 * (guard + nv_a),
+                  out.data_ptr() + 8 * (guard + nv_a + nv_b),
+                  codes.data_ptr() + 4 * guard]
+    tbl["dst_len"] = [len(p) for p in pages]
+    tbl["nv"] = [nv_a, nv_b, nv_c, nv_d]
+    tbl["kind"] = [8, 8, 8, g._PQK_CODES]
+    tbl["flags"] = g._PQF_HAS_DEF
+    tbl["lut"] = [0, 0, 0, lut.data_ptr()]
+    tbl["code_lim"] = [0, 0, 0, 2]
+    assert g._VALPAGE_DT.itemsize == 48
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    K.pq_values_multi(torch.from_numpy(tbl.view(np.uint8)).to(dev), 4, err)
+    torch.cuda.synchronize()
+
+    e = int(err.item())
+    assert e != 0
+    # levels not all 1 (A), level section overruns (B), code out of range (D)
+    assert e == 1 | 2 | 16
+    got = out.cpu().numpy()
+    c0 = guard + nv_a + nv_b
+    assert (got[:c0] == sentinel).all()  # front guard and the bad pages
+    assert (got[c0 + nv_c:] == sentinel).all()
+    assert (got[c0:c0 + nv_c] == vals_c).all()
+    assert (codes.cpu().numpy() == 0x5A5A5A5A).all()
+
+    # the same table without the bad pages reports nothing
+    err.zero_()
+    good = tbl[2:3].copy()
+    K.pq_values_multi(torch.from_numpy(good.view(np.uint8)).to(dev), 1, err)
+    assert int(err.item()) == 0
