@@ -7,6 +7,7 @@ eager fallback; round-end native check).
 
 from __future__ import annotations
 
+import os
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -175,6 +176,23 @@ def _keys_valid_mask(cols: Sequence[Column]) -> Optional[torch.Tensor]:
     return m
 
 
+def _key_bounds(c: Column) -> Optional[Tuple[int, int]]:
+    """Known inclusive (lo, hi) of an unmasked small-range key column:
+    dictionary codes, bools, and integer/date32 columns with val_range.
+    None for anything else."""
+    if c.mask is not None:
+        return None
+    k = c.dtype.kind
+    if k == TypeKind.DICT:
+        return 0, max(0, len(c.dictionary) - 1)
+    if k == TypeKind.BOOL:
+        return 0, 1
+    if (c.dtype.is_integer or k == TypeKind.DATE32) and c.val_range:
+        lo, hi = c.val_range
+        return int(lo), int(hi)
+    return None
+
+
 def _try_pack_keys(key_cols: Sequence[Column]) -> Optional[Column]:
     """Pack small-range integer/dict/bool keys into ONE int64 column so the
     hash-table equality check reads 8 bytes instead of one random read per
@@ -182,17 +200,10 @@ def _try_pack_keys(key_cols: Sequence[Column]) -> Optional[Column]:
     shift = 0
     packed = None
     for c in key_cols:
-        if c.mask is not None:
+        bounds = _key_bounds(c)
+        if bounds is None:
             return None
-        k = c.dtype.kind
-        if k == TypeKind.DICT:
-            lo, hi = 0, max(0, len(c.dictionary) - 1)
-        elif k == TypeKind.BOOL:
-            lo, hi = 0, 1
-        elif (c.dtype.is_integer or k == TypeKind.DATE32) and c.val_range:
-            lo, hi = c.val_range
-        else:
-            return None
+        lo, hi = bounds
         width = max(1, int(hi - lo + 1).bit_length())
         if shift + width > 63:
             return None
@@ -204,10 +215,100 @@ def _try_pack_keys(key_cols: Sequence[Column]) -> Optional[Column]:
     return Column(bt.int64, packed)
 
 
-def groupby_build(key_cols: Sequence[Column]) -> Tuple[torch.Tensor, torch.Tensor]:
+FUSABLE = {"count", "size", "sum", "mean", "min", "max"}
+MAX_FUSED_AGGS = 4
+# below this many accumulator bytes agg_update_fused aggregates in LDS
+FUSED_LDS_BYTES = 48 * 1024
+
+# Dense (direct-address) groupby: when the keys' known ranges bound the key
+# space, the mixed-radix key is the group's slot and one kernel reads keys
+# and values and updates the accumulators (groupby_dense_fused).
+# BODO_AMD_DENSE_GROUPBY=0 turns the route off.
+DENSE_GROUPBY = os.environ.get("BODO_AMD_DENSE_GROUPBY", "1") != "0"
+DENSE_MAX_KEYS = 8
+DENSE_MAX_SLOTS = 1 << 25
+
+
+def dense_groupby_plan(key_cols: Sequence[Column], batch, n: int):
+    """Per-key (lo, radix) when the dense route applies to ``n`` rows
+    grouped by ``key_cols`` with the aggregates ``batch`` of (out_name,
+    column or None, func); None when the hash route has to run."""
+    if not 1 <= len(key_cols) <= DENSE_MAX_KEYS:
+        return None
+    if not 1 <= len(batch) <= MAX_FUSED_AGGS:
+        return None
+    for _, col, func in batch:
+        if func not in FUSABLE:
+            return None
+        if col is not None and col.dtype.kind == TypeKind.STRING:
+            return None
+    plan = []
+    nslots = 1
+    for c in key_cols:
+        bounds = _key_bounds(c)
+        if bounds is None:
+            return None
+        lo, hi = bounds
+        radix = hi - lo + 1
+        if radix < 1 or not -2**63 <= lo < 2**63:
+            return None
+        nslots *= radix
+        if nslots > DENSE_MAX_SLOTS:
+            return None
+        plan.append((lo, radix))
+    if nslots > 4 * n:
+        return None  # the table would outgrow the hash table of 2n slots
+    if len(batch) * nslots * 16 <= FUSED_LDS_BYTES:
+        return None  # few groups: the LDS kernel behind the hash route wins
+    return plan
+
+
+def slot_digits(slots: torch.Tensor, plan):
+    """Digit of every key in mixed-radix slot ids (the last key varies
+    fastest): the inverse of groupby_dense_fused's slot encoding."""
+    digits = []
+    for _, radix in reversed(plan):
+        digits.append(slots % radix)
+        slots = slots // radix
+    return digits[::-1]
+
+
+def _groupby_dense(keys, key_cols, batch, plan, n) -> Optional[Table]:
+    """Dense route of groupby_local; None when a key lay outside its
+    val_range, in which case nothing was computed."""
+    K = kernels()
+    device = key_cols[0].device
+    datas, masks, dtypes, ops_, init_fs, init_is, _, posts = \
+        _fused_specs(batch, {}, device)
+    flat = K.groupby_dense_fused(
+        [_data_mask8(c)[0] for c in key_cols],
+        [int(c.dtype.kind) for c in key_cols],
+        [lo for lo, _ in plan], [radix for _, radix in plan],
+        datas, masks, dtypes, ops_, init_fs, init_is, n)
+    if not flat:
+        return None
+    slots = flat[0]
+    ngroups = int(slots.numel())
+    out_cols = []
+    for c, (lo, _), digit in zip(key_cols, plan, slot_digits(slots, plan)):
+        data = (digit + lo).to(c.data.dtype)
+        col = Column(c.dtype, data, None, dictionary=c.dictionary,
+                     length=ngroups)
+        col.val_range = c.val_range
+        out_cols.append(col)
+    results = {}
+    _finish_fused(batch, posts, flat[1:], results)
+    out_cols += [results[o] for o, _, _ in batch]
+    return Table(list(keys) + [o for o, _, _ in batch], out_cols, ngroups)
+
+
+def groupby_build(key_cols: Sequence[Column],
+                  pack: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(row_gid, uniq_rows) of the hash build.  ``pack=False`` keeps keys
+    with known bounds out of the packed build, which relies on them."""
     K = kernels()
     n = len(key_cols[0])
-    pk = _try_pack_keys(key_cols)
+    pk = _try_pack_keys(key_cols) if pack else None
     if pk is not None:
         return K.groupby_build_packed(pk.data)
     h = hash_columns(key_cols)
@@ -232,13 +333,25 @@ def groupby_local(tbl: Table, keys: Sequence[str],
                 n = len(tbl)
     if n == 0:
         return _empty_gb_result(tbl, keys, aggs)
-    row_gid, uniq_rows = groupby_build(key_cols)
+    bounds_hold = True
+    if DENSE_GROUPBY:
+        batch = [(o, tbl.column(i) if i and tbl.has_column(i) else None, f)
+                 for o, i, f in aggs]
+        plan = dense_groupby_plan(key_cols, batch, n)
+        if plan is not None:
+            dense = _groupby_dense(keys, key_cols, batch, plan, n)
+            if dense is not None:
+                return dense
+            # a key lies outside its val_range: packing it with those
+            # bounds would merge groups or produce the packed table's
+            # empty-slot word, so the build below compares the key columns
+            bounds_hold = False
+    row_gid, uniq_rows = groupby_build(key_cols, pack=bounds_hold)
     ngroups = int(uniq_rows.numel())
     out_names = list(keys)
     out_cols = [_gather_any(tbl.column(k), uniq_rows) for k in keys]
     # fused path: batch simple aggs (count/size/sum/mean/min/max) into one
     # kernel pass sharing the row_gid read; complex aggs go one-by-one
-    FUSABLE = {"count", "size", "sum", "mean", "min", "max"}
     fused_batch = []
     results = {}
 
@@ -279,6 +392,19 @@ def _run_fused(batch, row_gid, ngroups, results):
                         and not c.dtype.is_float)
         for _, c, f in batch)
     datas, masks, dtypes, ops_, init_fs, init_is, wants, posts = \
+        _fused_specs(batch, clean_float if share_size else {},
+                     row_gid.device)
+    flat = K.agg_update_fused(datas, masks, dtypes, ops_, init_fs, init_is,
+                              wants, row_gid, ngroups)
+    _finish_fused(batch, posts, flat, results)
+
+
+def _fused_specs(batch, shared_mean, device):
+    """Kernel arguments of a fused batch of (out_name, col, func), and per
+    aggregate how `_finish_fused` turns (acc, cnt) into the result.  Means
+    over the columns flagged in ``shared_mean`` (by id) carry no valid count
+    of their own and divide by the batch's size count."""
+    datas, masks, dtypes, ops_, init_fs, init_is, wants, posts = \
         [], [], [], [], [], [], [], []
     for out_name, col, func in batch:
         is_float = col is not None and col.dtype.is_float
@@ -304,8 +430,8 @@ def _run_fused(batch, row_gid, ngroups, results):
                 ops_.append(_AGG_OP["sum_f64"])
                 init_fs.append(0.0)
                 init_is.append(0)
-                shared = (func == "mean" and share_size
-                          and clean_float.get(id(col), False))
+                shared = (func == "mean"
+                          and shared_mean.get(id(col), False))
                 wants.append(0 if shared else 1)
                 posts.append(("mean_shared" if shared else
                               ("mean" if func == "mean" else "acc_f64"), None))
@@ -329,7 +455,7 @@ def _run_fused(batch, row_gid, ngroups, results):
                 wants.append(1)
                 posts.append(("minmax_i64", col))
         if col_for_data is None:
-            data = torch.zeros(1, dtype=torch.int8, device=row_gid.device)
+            data = torch.zeros(1, dtype=torch.int8, device=device)
             mask8 = None
             dtypes.append(int(TypeKind.INT8))
         else:
@@ -337,8 +463,11 @@ def _run_fused(batch, row_gid, ngroups, results):
             dtypes.append(int(col_for_data.dtype.kind))
         datas.append(data)
         masks.append(mask8)
-    flat = K.agg_update_fused(datas, masks, dtypes, ops_, init_fs, init_is,
-                              wants, row_gid, ngroups)
+    return datas, masks, dtypes, ops_, init_fs, init_is, wants, posts
+
+
+def _finish_fused(batch, posts, flat, results):
+    """Results of a fused batch from its flat [acc, cnt] pairs."""
     shared_cnt = None
     for k in range(len(batch)):
         if posts[k][0] == "cnt_i64":
@@ -638,6 +767,95 @@ def _unify_dict_keys(bkeys: Sequence[Column],
     return out
 
 
+_SIGNED_INT_KINDS = (TypeKind.INT8, TypeKind.INT16, TypeKind.INT32,
+                     TypeKind.INT64)
+
+
+def _widen_int_keys(bkeys: Sequence[Column], pkeys: Sequence[Column]):
+    """The probe kernels read both sides of a key pair with the probe
+    column's type, so a pair of signed integer keys of different widths is
+    compared as int64 (the hashes are by value and do not change)."""
+    bkeys, pkeys = list(bkeys), list(pkeys)
+    for i, (b, p) in enumerate(zip(bkeys, pkeys)):
+        if b.dtype.kind != p.dtype.kind and b.dtype.kind in _SIGNED_INT_KINDS \
+                and p.dtype.kind in _SIGNED_INT_KINDS:
+            bkeys[i] = Column(bt.int64, b.data.long(), b.mask, length=len(b))
+            pkeys[i] = Column(bt.int64, p.data.long(), p.mask, length=len(p))
+    return bkeys, pkeys
+
+
+# Dense (direct-address) join: an inner join on one integer key whose build
+# side is unique and spans a small range probes a lookup table indexed by
+# key - min instead of hashing both sides.  BODO_AMD_DENSE_JOIN=0 turns the
+# route off.
+DENSE_JOIN = os.environ.get("BODO_AMD_DENSE_JOIN", "1") != "0"
+DENSE_JOIN_MAX_SPAN = 1 << 22
+_DENSE_JOIN_KINDS = (TypeKind.INT8, TypeKind.INT16, TypeKind.INT32,
+                     TypeKind.INT64, TypeKind.DATE32)
+
+
+def dense_join_eligible(bkeys: Sequence[Column], pkeys: Sequence[Column],
+                        how: str) -> bool:
+    """What can be told without looking at the build keys' values."""
+    if how != "inner" or len(bkeys) != 1 or len(pkeys) != 1:
+        return False
+    b, p = bkeys[0], pkeys[0]
+    if b.dtype.kind != p.dtype.kind or b.dtype.kind not in _DENSE_JOIN_KINDS:
+        return False
+    if b.mask is not None and p.mask is not None:
+        return False  # the hash route matches a null key with a null key
+    return len(b) <= DENSE_JOIN_MAX_SPAN
+
+
+def _dense_join_lut(bkey: Column):
+    """(lut, lo, dup) of a build key column: int32 lut[key - lo] = build
+    row, -1 where no row has that key; rows with a null key are left out.
+    ``dup`` is a device flag, set when two build rows share a key (the lut
+    is then unusable).  None when the keys span more than
+    DENSE_JOIN_MAX_SPAN.  One host sync, for the min and max."""
+    dev = bkey.device
+    data = bkey.data.long()
+    rows = torch.arange(len(bkey), dtype=torch.int32, device=dev)
+    if bkey.mask is not None:
+        data, rows = data[bkey.mask], rows[bkey.mask]
+    if int(data.numel()) == 0:
+        return (torch.full((1,), -1, dtype=torch.int32, device=dev), 0,
+                torch.zeros((), dtype=torch.bool, device=dev))
+    lo, hi = torch.stack(torch.aminmax(data)).tolist()
+    span = hi - lo + 1
+    if span > DENSE_JOIN_MAX_SPAN:
+        return None
+    idx = data - lo  # wraps to [0, span) in two's complement
+    per_key = torch.zeros(span, dtype=torch.int32, device=dev)
+    per_key.scatter_add_(0, idx, torch.ones_like(rows))
+    lut = torch.full((span,), -1, dtype=torch.int32, device=dev)
+    lut[idx] = rows
+    return lut, lo, (per_key > 1).any()
+
+
+def _join_dense(build: Table, probe: Table, bkey: Column, pkey: Column):
+    """(probe table, build table) of the matching rows in probe order, or
+    None when the hash route has to run."""
+    from . import take_table
+
+    built = _dense_join_lut(bkey)
+    if built is None:
+        return None
+    lut, lo, dup = built
+    pdata, pmask8 = _data_mask8(pkey)
+    out_build, misses = kernels().join_probe_dense(
+        pdata, pmask8, int(pkey.dtype.kind), len(probe), lut, lo)
+    n_miss, is_dup = torch.stack(
+        [misses[0], dup.to(torch.int64)]).tolist()
+    if is_dup:
+        return None
+    if n_miss:
+        out_probe = torch.nonzero(out_build >= 0, as_tuple=False).reshape(-1)
+        out_build = out_build[out_probe]
+        probe = take_table(probe, out_probe)
+    return probe, take_table(build, out_build)
+
+
 def join_local(left: Table, right: Table, left_on: Sequence[str],
                right_on: Sequence[str], how: str, suffixes=("_x", "_y")) -> Table:
     from . import take_table
@@ -660,6 +878,12 @@ def join_local(left: Table, right: Table, left_on: Sequence[str],
     pkeys = [probe.column(k) for k in left_on]
     bkeys = _unify_dict_keys(bkeys, pkeys)
     n_build, n_probe = len(build), len(probe)
+    if DENSE_JOIN and dense_join_eligible(bkeys, pkeys, how):
+        dense = _join_dense(build, probe, bkeys[0], pkeys[0])
+        if dense is not None:  # inner: never swapped
+            return _merge_joined(dense[0], dense[1], list(left_on),
+                                 list(right_on), suffixes, how)
+    bkeys, pkeys = _widen_int_keys(bkeys, pkeys)
     bh = hash_columns(bkeys) if n_build else torch.zeros(0, dtype=torch.int64, device=build.device)
     ph = hash_columns(pkeys) if n_probe else torch.zeros(0, dtype=torch.int64, device=build.device)
     heads, nxt = K.join_build(bh, n_build)

@@ -17,6 +17,7 @@
 #include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
 
+#include <cstring>
 #include <vector>
 
 #include "common.h"
@@ -443,7 +444,7 @@ __global__ void gb_assign_gid_kernel(const Slots table, int64_t chunk,
   for (int64_t s = start + threadIdx.x; s < stop; s += blockDim.x) {
     if (table.occupied(s)) {
       int32_t gid = (int32_t)(base + atomicAdd(&lds_cnt, 1));
-      slot_gid[s] = gid;
+      if (slot_gid != nullptr) slot_gid[s] = gid;
       uniq_rows[gid] = table.row(s);
     }
   }
@@ -453,6 +454,56 @@ __global__ void gb_rowgid_kernel(const uint32_t* __restrict__ row_slot,
                                  const int32_t* __restrict__ slot_gid,
                                  int32_t* __restrict__ row_gid, int64_t n) {
   GRID_STRIDE_LOOP(i, n) { row_gid[i] = slot_gid[row_slot[i]]; }
+}
+
+// Number the occupied slots of a table of `cap` slots: uniq_rows[gid] =
+// table.row(slot), and slot_gid[slot] = gid when asked for.  The count of
+// groups is the one device-to-host transfer; `extra_word` (a one-element
+// int64 device tensor, or null) travels with it and comes back in `extra`.
+struct CompactedSlots {
+  int64_t ngroups;
+  int64_t extra;
+  torch::Tensor slot_gid;   // int32 [cap], undefined unless asked for
+  torch::Tensor uniq_rows;  // int64 [max(ngroups, 1)]
+};
+
+template <typename Slots>
+static CompactedSlots compact_slots(Slots table, int64_t cap,
+                                    const torch::Device& dev,
+                                    bool want_slot_gid,
+                                    const torch::Tensor* extra_word) {
+  int block = 256;
+  int nblocks = 2048;
+  int64_t chunk = (cap + nblocks - 1) / nblocks;
+  auto block_counts = torch::zeros({nblocks},
+                                   torch::dtype(torch::kInt64).device(dev));
+  hipLaunchKernelGGL(gb_count_kernel<Slots>, dim3(nblocks), dim3(block), 0,
+                     cur_stream(), table, chunk, cap,
+                     (int64_t*)block_counts.data_ptr());
+  CHECK_HIP(hipGetLastError());
+  auto block_base = torch::zeros({nblocks}, torch::dtype(torch::kInt64).device(dev));
+  auto bb_tail = block_base.slice(0, 1, nblocks);
+  at::cumsum_out(bb_tail, block_counts.slice(0, 0, nblocks - 1), 0);
+  CompactedSlots out;
+  out.extra = 0;
+  if (extra_word == nullptr) {
+    out.ngroups = block_counts.sum().item<int64_t>();
+  } else {
+    auto both = torch::cat({block_counts.sum().reshape({1}), *extra_word}).cpu();
+    out.ngroups = both[0].item<int64_t>();
+    out.extra = both[1].item<int64_t>();
+  }
+  if (want_slot_gid)
+    out.slot_gid = torch::empty({cap}, torch::dtype(torch::kInt32).device(dev));
+  out.uniq_rows = torch::empty({std::max<int64_t>(out.ngroups, 1)},
+                               torch::dtype(torch::kInt64).device(dev));
+  hipLaunchKernelGGL(gb_assign_gid_kernel<Slots>, dim3(nblocks), dim3(block),
+                     0, cur_stream(), table, chunk, cap,
+                     (const int64_t*)block_base.data_ptr(),
+                     want_slot_gid ? (int32_t*)out.slot_gid.data_ptr() : nullptr,
+                     (int64_t*)out.uniq_rows.data_ptr());
+  CHECK_HIP(hipGetLastError());
+  return out;
 }
 
 // Skeleton shared by both group builds.  The caller supplies its table:
@@ -498,28 +549,11 @@ static std::vector<torch::Tensor> build_groups(
     }
     if (!grown) break;
   }
-  auto table = view();
-  int nblocks = 2048;
-  int64_t chunk = (cap + nblocks - 1) / nblocks;
-  auto block_counts = torch::zeros({nblocks},
-                                   torch::dtype(torch::kInt64).device(dev));
-  hipLaunchKernelGGL(gb_count_kernel<decltype(table)>, dim3(nblocks),
-                     dim3(block), 0, cur_stream(), table, chunk, cap,
-                     (int64_t*)block_counts.data_ptr());
-  CHECK_HIP(hipGetLastError());
-  auto block_base = torch::zeros({nblocks}, torch::dtype(torch::kInt64).device(dev));
-  auto bb_tail = block_base.slice(0, 1, nblocks);
-  at::cumsum_out(bb_tail, block_counts.slice(0, 0, nblocks - 1), 0);
-  int64_t ngroups = block_counts.sum().item<int64_t>();
-  auto slot_gid = torch::empty({cap}, torch::dtype(torch::kInt32).device(dev));
-  auto uniq_rows = torch::empty({std::max<int64_t>(ngroups, 1)},
-                                torch::dtype(torch::kInt64).device(dev));
-  hipLaunchKernelGGL(gb_assign_gid_kernel<decltype(table)>, dim3(nblocks),
-                     dim3(block), 0, cur_stream(), table, chunk, cap,
-                     (const int64_t*)block_base.data_ptr(),
-                     (int32_t*)slot_gid.data_ptr(),
-                     (int64_t*)uniq_rows.data_ptr());
-  CHECK_HIP(hipGetLastError());
+  auto groups = compact_slots(view(), cap, dev, /*want_slot_gid=*/true,
+                              nullptr);
+  int64_t ngroups = groups.ngroups;
+  auto& slot_gid = groups.slot_gid;
+  auto& uniq_rows = groups.uniq_rows;
   auto row_gid = torch::empty({n}, torch::dtype(torch::kInt32).device(dev));
   hipLaunchKernelGGL(gb_rowgid_kernel, dim3(grid_for(n, block)), dim3(block),
                      0, cur_stream(), (const uint32_t*)row_slot.data_ptr(),
@@ -896,6 +930,250 @@ std::vector<torch::Tensor> agg_update(
 }
 
 // ---------------------------------------------------------------------
+// dense groupby: keys of a small known range address the table directly.
+// slot = sum_k (key_k - lo_k) * stride_k in mixed radix is a perfect group
+// id, so one row pass reads every key and value column once and updates the
+// accumulators; no key packing, hash insert, row_slot or row_gid.
+//
+// Table layout: nslots rows of (1 + n_aggs) 64-bit words, word 0 the row
+// count of the slot (the `size` of its group), word 1 + k the accumulator
+// of aggregate k: a row's atomics fall into one or two cache lines.  An
+// aggregate over a column that can hold nulls or NaNs has an array of
+// per-slot *invalid* counts beside the table, touched by such rows only;
+// its valid count is size - invalid.
+// ---------------------------------------------------------------------
+
+#define MAX_DENSE_KEYS 8
+#define DENSE_MAX_SLOTS (int64_t(1) << 25)
+
+struct DenseKeys {
+  const void* data[MAX_DENSE_KEYS];
+  int dtype[MAX_DENSE_KEYS];
+  int64_t lo[MAX_DENSE_KEYS];
+  uint64_t radix[MAX_DENSE_KEYS];
+  uint64_t stride[MAX_DENSE_KEYS];
+  int nkeys;
+};
+
+struct DenseAgg {
+  ColumnDesc col;
+  int op;
+  int64_t* invalid;  // per-slot count of null/NaN rows, or nullptr
+};
+
+struct DenseAggs {
+  DenseAgg a[MAX_FUSED_AGGS];
+  int n_aggs;
+};
+
+// integer-family value of row i (key columns and dense join keys)
+DEV_INLINE int64_t load_int_key(const void* data, int dtype, int64_t i) {
+  switch (dtype) {
+    case BT_INT8: return ((const int8_t*)data)[i];
+    case BT_UINT8: case BT_BOOL: return ((const uint8_t*)data)[i];
+    case BT_INT16: return ((const int16_t*)data)[i];
+    case BT_UINT16: return ((const uint16_t*)data)[i];
+    case BT_INT32: case BT_DATE32: case BT_DICT:
+      return ((const int32_t*)data)[i];
+    case BT_UINT32: return ((const uint32_t*)data)[i];
+    default: return ((const int64_t*)data)[i];  // INT64, UINT64
+  }
+}
+
+static int64_t int_key_width(int64_t dtype) {
+  switch (dtype) {
+    case BT_INT8: case BT_UINT8: case BT_BOOL: return 1;
+    case BT_INT16: case BT_UINT16: return 2;
+    case BT_INT32: case BT_DATE32: case BT_DICT: case BT_UINT32: return 4;
+    case BT_INT64: case BT_UINT64: return 8;
+  }
+  return 0;  // not an integer-family key
+}
+
+__global__ void dense_init_kernel(uint64_t* __restrict__ table, int words,
+                                  uint64_t i0, uint64_t i1, uint64_t i2,
+                                  uint64_t i3, int64_t nslots) {
+  GRID_STRIDE_LOOP(j, nslots * words) {
+    int w = (int)(j % words);
+    table[j] = w == 0 ? 0ull : w == 1 ? i0 : w == 2 ? i1 : w == 3 ? i2 : i3;
+  }
+}
+
+__global__ void groupby_dense_fused_kernel(const DenseKeys keys,
+                                           const DenseAggs aggs,
+                                           uint64_t* __restrict__ table,
+                                           int64_t* __restrict__ err,
+                                           int64_t n) {
+  const int words = 1 + aggs.n_aggs;
+  GRID_STRIDE_LOOP(i, n) {
+    uint64_t slot = 0;
+    bool in_range = true;
+    for (int k = 0; k < keys.nkeys; ++k) {
+      uint64_t digit = (uint64_t)load_int_key(keys.data[k], keys.dtype[k], i) -
+                       (uint64_t)keys.lo[k];
+      in_range &= digit < keys.radix[k];
+      slot += digit * keys.stride[k];
+    }
+    if (!in_range) {  // val_range lied: the host reruns the hash route
+      *err = 1;
+      continue;
+    }
+    uint64_t* row = table + slot * words;
+    atomicAdd((unsigned long long*)row, 1ull);
+    for (int k = 0; k < aggs.n_aggs; ++k) {
+      int op = aggs.a[k].op;
+      if (op == AGG_SIZE) continue;
+      AggValue v = agg_load(aggs.a[k].col, i);
+      if (!v.valid) {
+        atomicAdd((unsigned long long*)&aggs.a[k].invalid[slot], 1ull);
+        continue;
+      }
+      agg_apply(op, (double*)(row + 1 + k), v.dv, v.iv, i);
+    }
+  }
+}
+
+struct DenseSlots {  // dense table: occupied = row count != 0, row = slot
+  const uint64_t* table;
+  int words;
+  DEV_INLINE bool occupied(int64_t s) const { return table[s * words] != 0; }
+  DEV_INLINE int64_t row(int64_t s) const { return s; }
+};
+
+// accumulators and valid counts of the occupied slots, in group order:
+// acc[k][g] = word 1 + k of slot_ids[g]; cnt[g] = size (row 0 of cnt) and
+// cnt[1 + k][g] = size - invalid_k where aggregate k has invalid counts
+__global__ void dense_gather_kernel(const uint64_t* __restrict__ table,
+                                    const DenseAggs aggs,
+                                    const int64_t* __restrict__ slot_ids,
+                                    uint64_t* __restrict__ acc,
+                                    int64_t* __restrict__ cnt,
+                                    int64_t ngroups) {
+  const int words = 1 + aggs.n_aggs;
+  GRID_STRIDE_LOOP(g, ngroups) {
+    int64_t s = slot_ids[g];
+    const uint64_t* row = table + s * words;
+    int64_t size = (int64_t)row[0];
+    cnt[g] = size;
+    for (int k = 0; k < aggs.n_aggs; ++k) {
+      acc[k * ngroups + g] = row[1 + k];
+      if (aggs.a[k].invalid != nullptr)
+        cnt[(1 + k) * ngroups + g] = size - aggs.a[k].invalid[s];
+    }
+  }
+}
+
+// Returns {} when a key fell outside its [lo, lo + radix): nothing of the
+// result is valid then.  Otherwise [slot_ids, acc_0, cnt_0, acc_1, ...]:
+// slot_ids int64 [ngroups], and per aggregate what agg_update_fused returns
+// with want_count set (aggregates that cannot be invalid share one cnt).
+std::vector<torch::Tensor> groupby_dense_fused(
+    std::vector<torch::Tensor> key_datas, std::vector<int64_t> key_dtypes,
+    std::vector<int64_t> key_los, std::vector<int64_t> key_radices,
+    std::vector<torch::Tensor> datas,
+    std::vector<c10::optional<torch::Tensor>> masks,
+    std::vector<int64_t> dtypes, std::vector<int64_t> ops,
+    std::vector<double> init_fs, std::vector<int64_t> init_is, int64_t n) {
+  int nkeys = (int)key_datas.size();
+  int n_aggs = (int)datas.size();
+  TORCH_CHECK(nkeys >= 1 && nkeys <= MAX_DENSE_KEYS, "groupby_dense_fused: ",
+              nkeys, " keys");
+  TORCH_CHECK(n_aggs >= 1 && n_aggs <= MAX_FUSED_AGGS);
+  TORCH_CHECK(n >= 1);
+  TORCH_CHECK((int)key_dtypes.size() == nkeys && (int)key_los.size() == nkeys &&
+              (int)key_radices.size() == nkeys);
+  TORCH_CHECK((int)masks.size() == n_aggs && (int)dtypes.size() == n_aggs &&
+              (int)ops.size() == n_aggs && (int)init_fs.size() == n_aggs &&
+              (int)init_is.size() == n_aggs);
+  auto dev = key_datas[0].device();
+  DenseKeys keys = {};
+  keys.nkeys = nkeys;
+  int64_t nslots = 1;
+  for (int k = nkeys - 1; k >= 0; --k) {  // last key varies fastest
+    int64_t width = int_key_width(key_dtypes[k]);
+    TORCH_CHECK(width != 0, "groupby_dense_fused: key dtype ", key_dtypes[k]);
+    TORCH_CHECK(key_datas[k].is_contiguous() && key_datas[k].numel() >= n &&
+                key_datas[k].element_size() == width,
+                "groupby_dense_fused: key ", k, " storage");
+    TORCH_CHECK(key_radices[k] >= 1 && key_radices[k] <= DENSE_MAX_SLOTS);
+    keys.data[k] = key_datas[k].data_ptr();
+    keys.dtype[k] = (int)key_dtypes[k];
+    keys.lo[k] = key_los[k];
+    keys.radix[k] = (uint64_t)key_radices[k];
+    keys.stride[k] = (uint64_t)nslots;
+    nslots *= key_radices[k];
+    TORCH_CHECK(nslots <= DENSE_MAX_SLOTS, "groupby_dense_fused: key space");
+  }
+  DenseAggs aggs = {};
+  aggs.n_aggs = n_aggs;
+  uint64_t init_bits[MAX_FUSED_AGGS] = {};
+  std::vector<torch::Tensor> invalids(n_aggs);
+  for (int k = 0; k < n_aggs; ++k) {
+    TORCH_CHECK(ops[k] >= AGG_SUM_F64 && ops[k] <= AGG_SIZE,
+                "groupby_dense_fused: unsupported op ", ops[k]);
+    aggs.a[k].op = (int)ops[k];
+    aggs.a[k].col = make_desc(datas[k], masks[k], c10::nullopt, c10::nullopt,
+                              dtypes[k], n);
+    bool nullable = false;
+    if (ops[k] != AGG_SIZE) {
+      TORCH_CHECK(datas[k].is_contiguous() && datas[k].numel() >= n,
+                  "groupby_dense_fused: value column ", k);
+      TORCH_CHECK(!masks[k].has_value() ||
+                  (masks[k]->is_contiguous() && masks[k]->numel() >= n &&
+                   masks[k]->element_size() == 1));
+      nullable = masks[k].has_value() || dtypes[k] == BT_FLOAT32 ||
+                 dtypes[k] == BT_FLOAT64;
+    }
+    if (nullable) {
+      invalids[k] = torch::zeros({nslots},
+                                 torch::dtype(torch::kInt64).device(dev));
+      aggs.a[k].invalid = (int64_t*)invalids[k].data_ptr();
+    }
+    if (is_f64_acc(ops[k])) {
+      memcpy(&init_bits[k], &init_fs[k], 8);
+    } else {
+      init_bits[k] = (uint64_t)init_is[k];
+    }
+  }
+  int words = 1 + n_aggs;
+  auto i64 = torch::dtype(torch::kInt64).device(dev);
+  auto table = torch::empty({nslots * words}, i64);
+  auto err = torch::zeros({1}, i64);
+  int block = 256;
+  hipLaunchKernelGGL(dense_init_kernel, dim3(grid_for(nslots * words, block)),
+                     dim3(block), 0, cur_stream(),
+                     (uint64_t*)table.data_ptr(), words, init_bits[0],
+                     init_bits[1], init_bits[2], init_bits[3], nslots);
+  CHECK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(groupby_dense_fused_kernel, dim3(grid_for(n, block)),
+                     dim3(block), 0, cur_stream(), keys, aggs,
+                     (uint64_t*)table.data_ptr(), (int64_t*)err.data_ptr(), n);
+  CHECK_HIP(hipGetLastError());
+  DenseSlots view{(const uint64_t*)table.data_ptr(), words};
+  auto groups = compact_slots(view, nslots, dev, /*want_slot_gid=*/false, &err);
+  if (groups.extra != 0) return {};
+  int64_t ngroups = groups.ngroups;
+  auto acc = torch::empty({n_aggs, ngroups}, i64);
+  auto cnt = torch::empty({1 + n_aggs, ngroups}, i64);
+  if (ngroups) {
+    hipLaunchKernelGGL(dense_gather_kernel, dim3(grid_for(ngroups, block)),
+                       dim3(block), 0, cur_stream(),
+                       (const uint64_t*)table.data_ptr(), aggs,
+                       (const int64_t*)groups.uniq_rows.data_ptr(),
+                       (uint64_t*)acc.data_ptr(), (int64_t*)cnt.data_ptr(),
+                       ngroups);
+    CHECK_HIP(hipGetLastError());
+  }
+  std::vector<torch::Tensor> out = {groups.uniq_rows.slice(0, 0, ngroups)};
+  for (int k = 0; k < n_aggs; ++k) {
+    auto a = acc.select(0, k);
+    out.push_back(is_f64_acc(ops[k]) ? a.view(torch::kFloat64) : a);
+    out.push_back(cnt.select(0, invalids[k].defined() ? 1 + k : 0));
+  }
+  return out;
+}
+
+// ---------------------------------------------------------------------
 // hash join: bucket-chained build table + two-pass probe
 // ---------------------------------------------------------------------
 
@@ -1055,6 +1333,73 @@ std::vector<torch::Tensor> join_probe(
   return {out_probe, out_build};
 }
 
+// Dense probe for a unique integer build key of small range: lut[key - lo]
+// is the build row of that key or -1.  One pass: out_build[i] is the build
+// row matching probe row i, or -1 for a null key, a key outside the table
+// or an empty entry; *misses counts the -1 rows.
+__global__ void join_probe_dense_kernel(const void* __restrict__ pdata,
+                                        const uint8_t* __restrict__ pmask,
+                                        int pdtype,
+                                        const int32_t* __restrict__ lut,
+                                        uint64_t lut_len, int64_t lo,
+                                        int64_t* __restrict__ out_build,
+                                        int64_t* __restrict__ misses,
+                                        int64_t n_probe) {
+  int64_t local = 0;
+  GRID_STRIDE_LOOP(i, n_probe) {
+    int64_t b = -1;
+    if (pmask == nullptr || pmask[i]) {
+      uint64_t d = (uint64_t)load_int_key(pdata, pdtype, i) - (uint64_t)lo;
+      if (d < lut_len) b = lut[d];
+    }
+    out_build[i] = b;
+    local += b < 0;
+  }
+  __shared__ int64_t red[256];
+  red[threadIdx.x] = local;
+  __syncthreads();
+  for (int w = blockDim.x / 2; w > 0; w >>= 1) {
+    if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0 && red[0])
+    atomicAdd((unsigned long long*)misses, (unsigned long long)red[0]);
+}
+
+// returns [out_build int64 [n_probe], misses int64 [1]] (both on device)
+std::vector<torch::Tensor> join_probe_dense(
+    torch::Tensor pdata, c10::optional<torch::Tensor> pmask, int64_t pdtype,
+    int64_t n_probe, torch::Tensor lut, int64_t lo) {
+  auto dev = lut.device();
+  int64_t width = int_key_width(pdtype);
+  TORCH_CHECK(width != 0 && pdtype != BT_DICT && pdtype != BT_BOOL,
+              "join_probe_dense: key dtype ", pdtype);
+  TORCH_CHECK(n_probe >= 0 && pdata.is_contiguous() &&
+              pdata.numel() >= n_probe && pdata.element_size() == width,
+              "join_probe_dense: key storage");
+  TORCH_CHECK(!pmask.has_value() ||
+              (pmask->is_contiguous() && pmask->numel() >= n_probe &&
+               pmask->element_size() == 1), "join_probe_dense: mask");
+  TORCH_CHECK(lut.scalar_type() == torch::kInt32 && lut.is_contiguous() &&
+              lut.numel() >= 1, "join_probe_dense: lut");
+  auto i64 = torch::dtype(torch::kInt64).device(dev);
+  auto out_build = torch::empty({n_probe}, i64);
+  auto misses = torch::zeros({1}, i64);
+  if (n_probe) {
+    int block = 256;
+    hipLaunchKernelGGL(join_probe_dense_kernel, dim3(grid_for(n_probe, block)),
+                       dim3(block), 0, cur_stream(), pdata.data_ptr(),
+                       pmask.has_value() ? (const uint8_t*)pmask->data_ptr()
+                                         : nullptr,
+                       (int)pdtype, (const int32_t*)lut.data_ptr(),
+                       (uint64_t)lut.numel(), lo,
+                       (int64_t*)out_build.data_ptr(),
+                       (int64_t*)misses.data_ptr(), n_probe);
+    CHECK_HIP(hipGetLastError());
+  }
+  return {out_build, misses};
+}
+
 // ---------------------------------------------------------------------
 // Parquet RLE/bit-packed hybrid expansion (on-GPU parquet decode path;
 // reference role: cudf::io::read_parquet in gpu_read_parquet.h, here a
@@ -1174,6 +1519,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("agg_update", &agg_update, "aggregate update");
   m.def("join_build", &join_build, "hash join build");
   m.def("join_probe", &join_probe, "hash join probe");
+  m.def("groupby_dense_fused", &groupby_dense_fused,
+        "direct-address groupby: keys + fused aggregates in one row pass");
+  m.def("join_probe_dense", &join_probe_dense,
+        "direct-address probe of a unique small-range integer build key");
   m.def("pq_decompress", &pq_decompress,
         "page-parallel snappy decompress (one wave/page)");
   m.def("pq_decompress_multi", &pq_decompress_multi,
