@@ -17,12 +17,25 @@ need no mask, no per-chunk launches and no concatenation.  Integer and
 date32 columns take val_range from the footer's min/max.  Chunks outside
 these paths (other codecs, v2 pages, BOOLEAN/INT96/FIXED_LEN, mixed
 plain/dict) take the older per-page route and then the host Arrow decoder.
+
+The pipelined reader is built from parts that run without a GPU, so CPU
+tests drive it end to end against kernel simulators: _scan_chunks (footers
+to _Chunk records), _Prefetcher (reader threads, staging slots and their
+ordered gate), _GroupTables (the absolute-address page tables of a group,
+computed on the host) and _GroupDecoder (the launches of a group).  The
+one device switch is in _Staging and _record_event: off CUDA the staging
+buffers are ordinary memory and an event is None, which waits for nothing.
 """
 
 from __future__ import annotations
 
+import glob
 import os
 import struct
+import threading
+import time
+from concurrent.futures import ThreadPoolExecutor
+from dataclasses import dataclass
 from typing import List, Optional, Tuple
 
 import numpy as np
@@ -152,41 +165,76 @@ def _runs_blob(runs) -> np.ndarray:
     return arr
 
 
-class _PinnedUploader:
-    """Reusable pinned host staging for chunk uploads: double-buffered so the
-    host memcpy into one buffer overlaps the async H2D copy from the other
-    (events guard reuse)."""
+def _record_event(device):
+    """An event recorded on the device's current stream.  None when the
+    device is not CUDA: work there is done when the call returns, and
+    _wait_event(None) waits for nothing."""
+    if torch.device(device).type != "cuda":
+        return None
+    ev = torch.cuda.Event()
+    ev.record()
+    return ev
 
-    def __init__(self):
-        self.bufs = [None, None]
-        self.events = [None, None]
-        self.i = 0
 
-    def upload(self, np_u8: np.ndarray, device) -> torch.Tensor:
-        n = len(np_u8)
-        if not torch.cuda.is_available():
-            return torch.from_numpy(np_u8.copy()).to(device)
-        i = self.i
-        self.i = 1 - i
+def _wait_event(ev) -> None:
+    if ev is not None:
+        ev.synchronize()
+
+
+class _Staging:
+    """A ring of pinned host buffers for async copies to the device.
+    take(k, n, device) gives buffer k % len of at least n bytes once the
+    previous copy out of it has finished; after queueing the next copy out
+    the user hands its event to sent(k, ev).  For a device that is not CUDA
+    the buffers are ordinary memory and the events None."""
+
+    def __init__(self, n_bufs: int, min_bytes: int):
+        self.min_bytes = min_bytes
+        self.bufs: list = [None] * n_bufs
+        self.pinned = [False] * n_bufs
+        self.events: list = [None] * n_bufs
+        self.turn = 0
+
+    def next_turn(self) -> int:
+        """Round-robin k for users that have no task numbers of their own."""
+        k = self.turn
+        self.turn = (k + 1) % len(self.bufs)
+        return k
+
+    def take(self, k: int, n: int, device) -> torch.Tensor:
+        i = k % len(self.bufs)
+        _wait_event(self.events[i])  # the copy out of this buffer is done
+        self.events[i] = None
+        pin = torch.device(device).type == "cuda"
         buf = self.bufs[i]
-        if buf is None or buf.numel() < n:
-            buf = torch.empty(max(n, 1 << 22), dtype=torch.uint8,
-                              pin_memory=True)
-            self.bufs[i] = buf
-            self.events[i] = None
-        ev = self.events[i]
-        if ev is not None:
-            ev.synchronize()  # previous async copy out of this buffer done
-        buf[:n].copy_(torch.from_numpy(np_u8))
-        out = torch.empty(n, dtype=torch.uint8, device=device)
-        out.copy_(buf[:n], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        self.events[i] = ev
-        return out
+        if buf is None or buf.numel() < n or self.pinned[i] != pin:
+            buf = torch.empty(max(n, self.min_bytes), dtype=torch.uint8,
+                              pin_memory=pin)
+            self.bufs[i], self.pinned[i] = buf, pin
+        return buf
+
+    def sent(self, k: int, ev) -> None:
+        self.events[k % len(self.bufs)] = ev
 
 
-_UPLOADER = _PinnedUploader()
+# chunk uploads outside the pipelined reader: double-buffered so the host
+# memcpy into one buffer overlaps the async H2D copy from the other
+_CHUNK_STAGING = _Staging(2, 1 << 22)
+# page tables of a group: written into a pinned buffer and copied with
+# non_blocking=True, so the consumer thread never waits for the chunk
+# copies queued before them
+_TABLE_STAGING = _Staging(4, 1 << 21)
+
+
+def _upload_staged(staging: _Staging, np_u8: np.ndarray,
+                   dev_out: torch.Tensor) -> None:
+    """Copy host bytes to dev_out through the ring's next buffer."""
+    n = len(np_u8)
+    k = staging.next_turn()
+    buf = staging.take(k, n, dev_out.device)
+    buf.numpy()[:n] = np_u8
+    dev_out.copy_(buf[:n], non_blocking=True)
+    staging.sent(k, _record_event(dev_out.device))
 
 # decode-path counters (tests assert the batched path actually ran)
 STATS = {"batched": 0, "slow": 0, "direct": 0}
@@ -380,8 +428,10 @@ class _ChunkReader:
         if self._dev is not None:
             src_dev = self._dev
         else:
-            src_dev = _UPLOADER.upload(
-                np.frombuffer(self.buf, dtype=np.uint8), device)
+            src_dev = torch.empty(len(self.buf), dtype=torch.uint8,
+                                  device=device)
+            _upload_staged(_CHUNK_STAGING,
+                           np.frombuffer(self.buf, dtype=np.uint8), src_dev)
         metas_dev = torch.from_numpy(metas.view(np.uint8)).to(device) \
             if upload_metas else None
         scratch_size = int(((d_usize + 7) & ~7).sum()) + 16
@@ -515,7 +565,7 @@ class _ChunkReader:
                 p = 0
                 mask_t: Optional[torch.Tensor] = None
                 n_valid = nv
-                if self._max_def() > 0:
+                if self.max_def > 0:
                     (lvl_len,) = struct.unpack_from("<i", pb, p)
                     lv_runs, got = _parse_rle_runs(pb, p + 4, p + 4 + lvl_len,
                                                    1, nv)
@@ -606,9 +656,6 @@ class _ChunkReader:
                 else mask_parts[0]
         return vals, (dict_vals if use_dict_col else None), mask
 
-    def _max_def(self) -> int:
-        return self.max_def
-
     def _decode_plain(self, buf: bytes, pos: int, nv: int):
         if self.phys == "BYTE_ARRAY":
             out = []
@@ -631,9 +678,6 @@ def _dev_bytes(pb: bytes, device) -> torch.Tensor:
 def read_shard_gpu(path: str, columns, ctx) -> Optional[Table]:
     """Read a parquet file (or list) with device-side decode; returns None
     when the file layout is outside the fast path."""
-    import glob
-    import os
-
     if os.path.isdir(path):
         files = sorted(glob.glob(os.path.join(path, "*.parquet")))
     else:
@@ -776,27 +820,78 @@ def _direct_chunk_kind(cm, field: pa.Field) -> Optional[str]:
     return None
 
 
+@dataclass(slots=True)
+class _Chunk:
+    """One column chunk of a shard, as the footer describes it."""
+
+    path: str
+    rg: int
+    cm: object  # pyarrow ColumnChunkMetaData
+    field: pa.Field
+    start: int  # byte range of the chunk in the file
+    size: int
+    first_of_rg: bool  # first selected chunk of its row group
+    row0: int  # first row of the row group in the shard
+    rows: int  # rows of the row group
+
+    @property
+    def name(self) -> str:
+        return self.cm.path_in_schema
+
+
+def _scan_chunks(my, columns) -> Tuple[List[_Chunk], List[str], int]:
+    """The selected column chunks of the (file, row group) pieces in shard
+    order, the output column names (as the last piece has them) and the
+    shard's row count."""
+    chunks: List[_Chunk] = []
+    pf_cache: dict = {}
+    names: List[str] = []
+    total_rows = 0
+    for fp, rg in my:
+        pf = pf_cache.get(fp)
+        if pf is None:
+            pf = pq.ParquetFile(fp)
+            pf_cache[fp] = pf
+        schema = pf.schema_arrow
+        rgm = pf.metadata.row_group(rg)
+        names = columns or [schema.field(i).name
+                            for i in range(len(schema.names))]
+        first = True
+        for ci in range(rgm.num_columns):
+            cm = rgm.column(ci)
+            if cm.path_in_schema not in names:
+                continue
+            start, size = _chunk_range(cm)
+            chunks.append(_Chunk(fp, rg, cm, schema.field(cm.path_in_schema),
+                                 start, size, first, total_rows,
+                                 int(rgm.num_rows)))
+            first = False
+        total_rows += int(rgm.num_rows)
+    return chunks, names, total_rows
+
+
 class _DirectCol:
     """A shard column that its chunks are decoded into in place."""
 
     __slots__ = ("kind", "esize", "data", "field", "unifier")
 
 
-def _plan_direct(items, n_rgs: int, total_rows: int, device) -> dict:
+def _plan_direct(chunks: List[_Chunk], n_rgs: int, total_rows: int,
+                 device) -> dict:
     """name -> _DirectCol for the columns whose every chunk is eligible by
     the footer; their whole-shard tensors are allocated here, once."""
     by_name: dict = {}
-    for it in items:
-        by_name.setdefault(it[2].path_in_schema, []).append(it)
+    for c in chunks:
+        by_name.setdefault(c.name, []).append(c)
     plan = {}
     for name, its in by_name.items():
-        field = its[0][3]
-        if len(its) != n_rgs or any(it[3].type != field.type or
-                                    it[3].nullable != field.nullable
-                                    for it in its):
+        field = its[0].field
+        if len(its) != n_rgs or any(c.field.type != field.type or
+                                    c.field.nullable != field.nullable
+                                    for c in its):
             continue
-        kinds = {_direct_chunk_kind(it[2], it[3]) for it in its}
-        phys = {it[2].physical_type for it in its}
+        kinds = {_direct_chunk_kind(c.cm, c.field) for c in its}
+        phys = {c.cm.physical_type for c in its}
         if len(kinds) != 1 or None in kinds or len(phys) != 1:
             continue
         dc = _DirectCol()
@@ -814,51 +909,174 @@ def _plan_direct(items, n_rgs: int, total_rows: int, device) -> dict:
     return plan
 
 
-class _TableUploader:
-    """Pinned staging ring for the page tables of a group: the tables are
-    written into a pinned buffer and copied with non_blocking=True, so the
-    consumer thread never waits for the chunk copies queued before them.
-    An event per buffer guards its reuse."""
+@dataclass(slots=True)
+class _DirectInfo:
+    """Where a chunk that is decoded in place goes."""
 
-    def __init__(self, n: int = 4):
-        self.bufs = [None] * n
-        self.events = [None] * n
-        self.i = 0
-
-    def upload(self, host_u8: np.ndarray, dev_out: torch.Tensor) -> None:
-        n = len(host_u8)
-        i = self.i
-        self.i = (i + 1) % len(self.bufs)
-        ev = self.events[i]
-        if ev is not None:
-            ev.synchronize()  # the copy out of this buffer is done
-            self.events[i] = None
-        buf = self.bufs[i]
-        if buf is None or buf.numel() < n:
-            buf = torch.empty(max(n, 1 << 21), dtype=torch.uint8,
-                              pin_memory=True)
-            self.bufs[i] = buf
-        buf.numpy()[:n] = host_u8
-        dev_out.copy_(buf[:n], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        self.events[i] = ev
+    col: _DirectCol  # the shard column
+    row0: int  # first row of the chunk in it
+    lut: Optional[np.ndarray]  # chunk codes -> unified codes, or None
 
 
-_TABLES = _TableUploader()
+@dataclass(slots=True)
+class _GroupEntry:
+    """A chunk of the group being collected."""
+
+    name: str
+    reader: _ChunkReader
+    field: pa.Field
+    prep: Optional[_Prepared]  # None: outside the batched path, or finished
+    column: Optional[Column]  # the decoded chunk, unless it is direct
+    direct: Optional[_DirectInfo]
+
+
+class _GroupTables:
+    """Layout and host image of the one blob a group uploads: a _PAGEPTR_DT
+    entry per page of every prepared chunk (pq_decompress_multi), then a
+    _VALPAGE_DT entry per page of the direct chunks (pq_values_multi), then
+    their code tables, each at an 8-byte-aligned offset.  Needs no GPU: the
+    addresses come from the tensors the chunks were prepared with."""
+
+    def __init__(self, preps: List[_Prepared], directs: List[_GroupEntry]):
+        self.preps, self.directs = preps, directs
+        self.n_dec = sum(p.n_pages for p in preps)
+        self.n_val = sum(e.prep.n_pages for e in directs)
+        self.dec_bytes = self.n_dec * _PAGEPTR_DT.itemsize
+        self.val_bytes = self.n_val * _VALPAGE_DT.itemsize
+        self.lut_at = []  # blob offset of each direct chunk's code table
+        self.nbytes = self.dec_bytes + self.val_bytes
+        for e in directs:
+            self.lut_at.append(self.nbytes)
+            if e.direct.lut is not None:
+                self.nbytes += (e.direct.lut.nbytes + 7) & ~7
+
+    def fill(self, blob_addr: int) -> np.ndarray:
+        """The blob's bytes, given the device address it will live at."""
+        host = np.zeros(self.nbytes, dtype=np.uint8)
+        tbl = host[:self.dec_bytes].view(_PAGEPTR_DT)
+        at = 0
+        for p in self.preps:
+            v = tbl[at:at + p.n_pages]
+            v["src"] = p.src_dev.data_ptr() + p.metas["src_off"]
+            v["dst"] = p.scratch.data_ptr() + p.metas["dst_off"]
+            v["src_len"] = p.metas["src_len"]
+            v["dst_len"] = p.metas["dst_len"]
+            v["flags"] = p.metas["flags"] & _PQF_SNAPPY
+            at += p.n_pages
+        vt = host[self.dec_bytes:self.dec_bytes + self.val_bytes] \
+            .view(_VALPAGE_DT)
+        at = 0
+        for e, la in zip(self.directs, self.lut_at):
+            p, dc, lut = e.prep, e.direct.col, e.direct.lut
+            v = vt[at:at + p.n_pages]
+            v["page"] = p.scratch.data_ptr() + p.metas["dst_off"]
+            v["out"] = dc.data.data_ptr() + \
+                (e.direct.row0 + p.metas["val_off"]) * dc.esize
+            v["dst_len"] = p.metas["dst_len"]
+            v["nv"] = p.metas["nv"]
+            v["kind"] = dc.esize if dc.kind == "plain" else _PQK_CODES
+            v["flags"] = p.metas["flags"] & _PQF_HAS_DEF
+            if dc.kind == "dict":
+                v["code_lim"] = len(p.dict_vals)
+                if lut is not None:
+                    v["lut"] = blob_addr + la
+                    host[la:la + lut.nbytes] = lut.view(np.uint8)
+            at += p.n_pages
+        return host
+
+
+class _Prefetcher:
+    """Reader threads that pull byte ranges of files into a ring of pinned
+    staging buffers ahead of one consumer that takes them in order:
+
+        with _Prefetcher(ranges, n_slots, device) as pf:
+            for k in range(len(ranges)):
+                buf = pf.get(k)          # task k's bytes, pinned
+                ... queue the async copy of buf to the device ...
+                pf.release(k, _record_event(device))
+
+    DETERMINISTIC slot assignment: task k uses slot k % N once the
+    consumer is done with the slot's previous occupant, task k-N.  The
+    consumer takes tasks in order, so the gate is one counter of tasks it
+    has let go of.  A shared free-slot queue deadlocked: workers for tasks
+    AHEAD of the consumer could hoard every released slot while the
+    consumer waited on the one starved task (observed as all threads
+    parked in slot_q.get on 600-chunk shards); a semaphore per slot let
+    task k+N take the slot from a task k that was slow to wake up.
+
+    Leaving the with block on any path sets the stop flag, wakes the
+    waiting workers and shuts the pool down before it returns."""
+
+    def __init__(self, ranges, n_slots: int, device):
+        self.ranges = ranges  # (path, start, size) of task k
+        self.device = device
+        self.n_slots = n_slots
+        self.slots = _Staging(n_slots, 1 << 24)
+        self.gate = threading.Condition()
+        self.released = 0  # tasks 0 .. released-1 no longer need their slots
+        self.stop = False  # the consumer left early: fetches return at once
+        self.pool = ThreadPoolExecutor(max_workers=n_slots)
+        self.futs: list = []
+
+    def __enter__(self):
+        self.futs = [self.pool.submit(self._fetch, k)
+                     for k in range(len(self.ranges))]
+        return self
+
+    def __exit__(self, *exc) -> None:
+        with self.gate:
+            self.stop = True
+            self.gate.notify_all()
+        self.pool.shutdown(wait=True, cancel_futures=True)
+
+    def _fetch(self, k: int) -> None:
+        with self.gate:
+            while self.released <= k - self.n_slots and not self.stop:
+                self.gate.wait()
+        if not self.stop:
+            self._read(k)
+
+    def _read(self, k: int) -> None:
+        path, start, size = self.ranges[k]
+        t0 = time.perf_counter()  # read time proper: not the slot wait
+        # take() waits for the previous H2D copy out of this slot
+        buf = self.slots.take(k, size, self.device)
+        with open(path, "rb") as f:
+            f.seek(start)
+            f.readinto(memoryview(buf.numpy()[:size]))
+        STATS["t_read"] = STATS.get("t_read", 0.0) + time.perf_counter() - t0
+
+    def get(self, k: int) -> torch.Tensor:
+        """Task k's bytes in its slot, once they are read."""
+        self.futs[k].result()
+        _, _, size = self.ranges[k]
+        return self.slots.bufs[k % self.n_slots][:size]
+
+    def release(self, k: int, copied) -> None:
+        """The consumer is done with task k's slot, bar the async copy out
+        of it that `copied` marks.  The event is stored before the counter
+        advances: the worker that gets the slot next waits for it."""
+        self.slots.sent(k, copied)
+        with self.gate:
+            self.released = k + 1
+            self.gate.notify_all()
+
+
 _RETRY = object()  # the direct read gave up: read again without it
 
 
 def _read_pieces_pipelined(my, columns, ctx) -> Optional[Table]:
     """Threaded disk->pinned prefetch overlapped with device decode.
 
-    N reader threads pull chunk byte ranges straight into a pool of pinned
-    staging buffers (`f.readinto`, no intermediate copy); the consumer
-    parses page headers (C++), snips the small dictionary page, issues the
-    async H2D copy and releases the slot for reuse once the copy's event
-    fires.  Chunks are decoded in groups of _GROUP_ROW_GROUPS row groups:
-    each is prepared as it arrives and one decompress launch covers the
-    pages of the whole group.
+    _scan_chunks lists the shard's column chunks (_Chunk) from the footers.
+    The _NSLOTS reader threads of a _Prefetcher pull their byte ranges
+    straight into a ring of pinned staging buffers (`f.readinto`, no
+    intermediate copy); the consumer parses page headers (C++), snips the
+    small dictionary page, issues the async H2D copy and releases the slot
+    for reuse once the copy's event fires.  Chunks are decoded in groups of
+    _GROUP_ROW_GROUPS row groups by a _GroupDecoder: each is prepared as it
+    arrives (_GroupEntry) and one decompress launch covers the pages of the
+    whole group.
 
     Columns whose every chunk is free of nulls by the footer statistics and
     holds PLAIN fixed-width values or string-dictionary codes are *direct*:
@@ -867,12 +1085,13 @@ def _read_pieces_pipelined(my, columns, ctx) -> Optional[Table]:
     definition levels and writes its values at the page's place in the
     shard column (dictionary codes through a per-chunk table into the
     shard's unified dictionary).  Both page tables and the code tables of a
-    group go up in one pinned, non-blocking copy.  The kernels report bad
-    pages through one error word read once at the end; if it is set, or
-    page headers contradict the footer, the shard is read again with the
-    direct path off.  All other chunks are finished one by one as before
-    and joined per column with ops.concat_columns.  Integer and date32
-    columns get val_range from the footer's min/max on both routes.
+    group are laid out on the host by _GroupTables and go up in one pinned,
+    non-blocking copy.  The kernels report bad pages through one error word
+    read once at the end; if it is set, or page headers contradict the
+    footer, the shard is read again with the direct path off.  All other
+    chunks are finished one by one as before and joined per column with
+    ops.concat_columns.  Integer and date32 columns get val_range from the
+    footer's min/max on both routes.
 
     Disk read overlaps PCIe upload and decode kernels of other chunks
     (reference role: bodo/io/parquet_reader.cpp prefetch +
@@ -886,227 +1105,143 @@ def _read_pieces_pipelined(my, columns, ctx) -> Optional[Table]:
     return _read_pieces_impl(my, columns, ctx, False)
 
 
-def _read_pieces_impl(my, columns, ctx, direct: bool):
-    import threading
-    import time
-    from concurrent.futures import ThreadPoolExecutor
+class _GroupDecoder:
+    """The consumer's decode state: the chunks of the group being collected
+    and the work already queued on the GPU."""
 
+    def __init__(self, device, err: Optional[torch.Tensor]):
+        self.device = device
+        self.err = err  # error word of pq_values_multi, or None: no direct
+        self.entries: List[_GroupEntry] = []
+        self.row_groups = 0  # row groups begun in the current group
+        # (event, chunk count) per flushed group or per-chunk fallback decode
+        self.inflight: list = []
+        self.pieces: dict = {}  # name -> Columns of the non-direct chunks
+
+    def queued(self, n_chunks: int) -> None:
+        """n_chunks more chunks were just queued on the current stream."""
+        self.inflight.append((_record_event(self.device), n_chunks))
+
+    def throttle(self, limit: int) -> None:
+        """Backpressure: keep at most ~2x the slot depth of decoded chunks
+        in flight on the GPU (unbounded enqueue ran the allocator far ahead
+        of execution on 600+-chunk shards); the group being prepared
+        counts, flushed work is waited for."""
+        while self.inflight and (sum(c for _, c in self.inflight)
+                                 + len(self.entries) >= limit):
+            done, _ = self.inflight.pop(0)
+            _wait_event(done)
+
+    def flush(self) -> bool:
+        """One decompress launch for every prepared chunk of the group and
+        one values call for its direct chunks, then the second half of
+        each other chunk's decode.  False when a chunk could not be
+        decoded on any route."""
+        if not self.entries:
+            return True
+        import bodo_amd_kernels as K
+
+        t0 = time.perf_counter()
+        preps = [e.prep for e in self.entries if e.prep is not None]
+        directs = [e for e in self.entries if e.direct is not None]
+        if preps:
+            tables = _GroupTables(preps, directs)
+            blob = torch.empty(tables.nbytes, dtype=torch.uint8,
+                               device=self.device)
+            _upload_staged(_TABLE_STAGING, tables.fill(blob.data_ptr()), blob)
+            K.pq_decompress_multi(blob[:tables.dec_bytes], tables.n_dec)
+            if tables.n_val:
+                K.pq_values_multi(
+                    blob[tables.dec_bytes:tables.dec_bytes + tables.val_bytes],
+                    tables.n_val, self.err)
+        for e in self.entries:
+            self._finish(e)
+        if preps:
+            self.queued(len(preps))
+        STATS["t_decode"] = STATS.get("t_decode", 0.0) + \
+            time.perf_counter() - t0
+        ok = True
+        for e in self.entries:
+            if e.direct is not None:
+                continue
+            if e.column is None:
+                ok = False
+                break
+            self.pieces.setdefault(e.name, []).append(e.column)
+        self.entries, self.row_groups = [], 0
+        return ok
+
+    def _finish(self, e: _GroupEntry) -> None:
+        """After the group's launches: count a direct chunk, decode the
+        second half of any other prepared chunk into e.column."""
+        if e.prep is None:
+            return
+        prep, e.prep = e.prep, None  # drop the chunk's source and scratch
+        if e.direct is not None:  # written in place by pq_values_multi
+            STATS["batched"] += 1
+            STATS["direct"] += 1
+            return
+        try:
+            col = e.reader._finish_batched(prep, self.device, e.field)
+        except Exception:
+            col = None
+        if col is not None:
+            STATS["batched"] += 1
+        else:  # today's per-chunk route, from the top
+            col = e.reader.decode_column(self.device, e.field)
+        e.column = col
+
+
+def _direct_info(dc: _DirectCol, prep: Optional[_Prepared],
+                 chunk: _Chunk) -> Optional[_DirectInfo]:
+    """Place of a chunk in its direct column, or None when its pages are
+    not what the footer promised."""
+    if (prep is None or prep.mode != dc.kind or prep.total_nv != chunk.rows
+            or (dc.kind == "dict" and (prep.dict_vals is None
+                                       or prep.dict_vals.dtype != object))):
+        return None
+    lut = dc.unifier.add(prep.dict_vals) if dc.kind == "dict" else None
+    return _DirectInfo(dc, chunk.row0, lut)
+
+
+def _read_pieces_impl(my, columns, ctx, direct: bool):
     import bodo_amd_kernels as K
 
     from .. import ops
 
     device = ctx.device
-    # (fp, rg, cm, field, start, size, first_of_rg, names, first row of the
-    #  row group in the shard, rows of the row group)
-    items = []
-    pf_cache = {}
-    total_rows = 0
-    for fp, rg in my:
-        pf = pf_cache.get(fp)
-        if pf is None:
-            pf = pq.ParquetFile(fp)
-            pf_cache[fp] = pf
-        schema = pf.schema_arrow
-        rgm = pf.metadata.row_group(rg)
-        names = columns or [schema.field(i).name
-                            for i in range(len(schema.names))]
-        first = True
-        for ci in range(rgm.num_columns):
-            cm = rgm.column(ci)
-            if cm.path_in_schema not in names:
-                continue
-            start, size = _chunk_range(cm)
-            items.append((fp, rg, cm, schema.field(cm.path_in_schema),
-                          start, size, first, names, total_rows,
-                          int(rgm.num_rows)))
-            first = False
-        total_rows += int(rgm.num_rows)
-    if not items:
+    chunks, names, total_rows = _scan_chunks(my, columns)
+    if not chunks:
         return None
-    plan = _plan_direct(items, len(my), total_rows, device) if direct else {}
+    plan = _plan_direct(chunks, len(my), total_rows, device) if direct else {}
     err = torch.zeros(1, dtype=torch.int32, device=device) if plan else None
-
-    slots = [{"t": None, "np": None, "ev": None} for _ in range(_NSLOTS)]
-    # DETERMINISTIC slot assignment: task k uses slot k % N once the
-    # consumer is done with the slot's previous occupant, task k-N.  The
-    # consumer takes tasks in order, so the gate is one counter of tasks it
-    # has let go of.  A shared free-slot queue deadlocked: workers for tasks
-    # AHEAD of the consumer could hoard every released slot while the
-    # consumer waited on the one starved task (observed as all threads
-    # parked in slot_q.get on 600-chunk shards); a semaphore per slot let
-    # task k+N take the slot from a task k that was slow to wake up.
-    gate = threading.Condition()
-    released = [0]  # tasks 0 .. released-1 no longer need their slots
-    stop = [False]  # the consumer left early: fetches return at once
-
-    def fetch(idx):
-        fp, start, size = items[idx][0], items[idx][4], items[idx][5]
-        i = idx % _NSLOTS
-        with gate:
-            while released[0] <= idx - _NSLOTS and not stop[0]:
-                gate.wait()
-        if stop[0]:
-            return i
-        t0 = time.perf_counter()  # read time proper: not the slot wait
-        s = slots[i]
-        if s["ev"] is not None:
-            s["ev"].synchronize()  # previous H2D out of this slot is done
-            s["ev"] = None
-        if s["t"] is None or s["t"].numel() < size:
-            s["t"] = torch.empty(max(size, 1 << 24), dtype=torch.uint8,
-                                 pin_memory=True)
-            s["np"] = s["t"].numpy()
-        with open(fp, "rb") as f:
-            f.seek(start)
-            f.readinto(memoryview(s["np"][:size]))
-        STATS["t_read"] = STATS.get("t_read", 0.0) + time.perf_counter() - t0
-        return i
-
-    ex = ThreadPoolExecutor(max_workers=_NSLOTS)
-    # (event, chunk count) per flushed group or per-chunk fallback decode
-    inflight: List[Tuple[torch.cuda.Event, int]] = []
-    # chunks of the current group: [name, reader, field, prepared-or-None,
-    # Column-or-None, direct (column, first row, code table) or None]
-    group: list = []
-    group_rgs = 0
-    pieces: dict = {}  # name -> Columns of the non-direct chunks, in order
+    dec = _GroupDecoder(device, err)
     metas_of: dict = {}  # name -> chunk metadata, for val_range
     field_of: dict = {}
-    seen_names: List[str] = []
-
-    def flush():
-        """One decompress launch for every prepared chunk of the group and
-        one values call for its direct chunks, then the second half of
-        each other chunk's decode."""
-        nonlocal group, group_rgs
-        if not group:
-            return True
-        t0 = time.perf_counter()
-        preps = [e[3] for e in group if e[3] is not None]
-        directs = [e for e in group if e[5] is not None]
-        if preps:
-            n_dec = sum(p.n_pages for p in preps)
-            n_val = sum(e[3].n_pages for e in directs)
-            dec_bytes = n_dec * _PAGEPTR_DT.itemsize
-            val_bytes = n_val * _VALPAGE_DT.itemsize
-            lut_at, nbytes = [], dec_bytes + val_bytes
-            for e in directs:
-                lut = e[5][2]
-                lut_at.append(nbytes)
-                if lut is not None:
-                    nbytes += (lut.nbytes + 7) & ~7
-            host = np.zeros(nbytes, dtype=np.uint8)
-            blob = torch.empty(nbytes, dtype=torch.uint8, device=device)
-            tbl = host[:dec_bytes].view(_PAGEPTR_DT)
-            at = 0
-            for p in preps:
-                v = tbl[at:at + p.n_pages]
-                v["src"] = p.src_dev.data_ptr() + p.metas["src_off"]
-                v["dst"] = p.scratch.data_ptr() + p.metas["dst_off"]
-                v["src_len"] = p.metas["src_len"]
-                v["dst_len"] = p.metas["dst_len"]
-                v["flags"] = p.metas["flags"] & _PQF_SNAPPY
-                at += p.n_pages
-            vt = host[dec_bytes:dec_bytes + val_bytes].view(_VALPAGE_DT)
-            at = 0
-            for e, la in zip(directs, lut_at):
-                p = e[3]
-                dc, row0, lut = e[5]
-                v = vt[at:at + p.n_pages]
-                v["page"] = p.scratch.data_ptr() + p.metas["dst_off"]
-                v["out"] = dc.data.data_ptr() + \
-                    (row0 + p.metas["val_off"]) * dc.esize
-                v["dst_len"] = p.metas["dst_len"]
-                v["nv"] = p.metas["nv"]
-                v["kind"] = dc.esize if dc.kind == "plain" else _PQK_CODES
-                v["flags"] = p.metas["flags"] & _PQF_HAS_DEF
-                if dc.kind == "dict":
-                    v["code_lim"] = len(p.dict_vals)
-                    if lut is not None:
-                        v["lut"] = blob.data_ptr() + la
-                        host[la:la + lut.nbytes] = lut.view(np.uint8)
-                at += p.n_pages
-            _TABLES.upload(host, blob)
-            K.pq_decompress_multi(blob[:dec_bytes], n_dec)
-            if n_val:
-                K.pq_values_multi(blob[dec_bytes:dec_bytes + val_bytes],
-                                  n_val, err)
-        for e in group:
-            if e[3] is None:
-                continue
-            if e[5] is not None:  # written in place by pq_values_multi
-                e[3] = None
-                STATS["batched"] += 1
-                STATS["direct"] += 1
-                continue
-            reader, field = e[1], e[2]
-            try:
-                col = reader._finish_batched(e[3], device, field)
-            except Exception:
-                col = None
-            e[3] = None  # drop the chunk's source and scratch tensors
-            if col is not None:
-                STATS["batched"] += 1
-            else:  # today's per-chunk route, from the top
-                col = reader.decode_column(device, field)
-            e[4] = col
-        if preps:
-            done = torch.cuda.Event()
-            done.record()
-            inflight.append((done, len(preps)))
-        STATS["t_decode"] = STATS.get("t_decode", 0.0) + \
-            time.perf_counter() - t0
-        ok = True
-        for e in group:
-            if e[5] is not None:
-                continue
-            if e[4] is None:
-                ok = False
-                break
-            pieces.setdefault(e[0], []).append(e[4])
-        group, group_rgs = [], 0
-        return ok
-
-    names = items[0][7]
-    try:
-        futs = [ex.submit(fetch, k) for k in range(len(items))]
-        for k, fut in enumerate(futs):
-            fp, rg, cm, field, start, size, first, names, row0, nrows = \
-                items[k]
-            if first:
-                if group_rgs >= _GROUP_ROW_GROUPS and not flush():
+    group_rgs, n_slots = _GROUP_ROW_GROUPS, _NSLOTS
+    ranges = [(c.path, c.start, c.size) for c in chunks]
+    with _Prefetcher(ranges, n_slots, device) as pf:
+        for k, c in enumerate(chunks):
+            if c.first_of_rg:
+                if dec.row_groups >= group_rgs and not dec.flush():
                     return None
-                group_rgs += 1
-            # backpressure: keep at most ~2x the slot depth of decoded
-            # chunks in flight on the GPU (unbounded enqueue ran the
-            # allocator far ahead of execution on 600+-chunk shards);
-            # the group being prepared counts, flushed work is waited for
-            while inflight and (sum(c for _, c in inflight) + len(group)
-                                >= 2 * _NSLOTS):
-                inflight.pop(0)[0].synchronize()
-            i = fut.result()
-            s = slots[i]
-            view = s["np"][:size]
+                dec.row_groups += 1
+            dec.throttle(2 * n_slots)
+            staged = pf.get(k)
             t0 = time.perf_counter()
-            hdrs = K.pq_parse_headers(torch.from_numpy(view)).numpy()
+            hdrs = K.pq_parse_headers(staged).numpy()
             dict_raw = None
             if hdrs.size and hdrs[0, 0] == PAGE_DICT:
                 b0, c0 = int(hdrs[0, 3]), int(hdrs[0, 2])
-                dict_raw = bytes(view[b0:b0 + c0])
-            dev = torch.empty(size, dtype=torch.uint8, device=device)
-            dev.copy_(s["t"][:size], non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-            s["ev"] = ev
-            with gate:
-                released[0] = k + 1
-                gate.notify_all()
-            name = cm.path_in_schema
-            dc = plan.get(name)
+                dict_raw = bytes(staged.numpy()[b0:b0 + c0])
+            dev = torch.empty(c.size, dtype=torch.uint8, device=device)
+            dev.copy_(staged, non_blocking=True)
+            pf.release(k, _record_event(device))
+            dc = plan.get(c.name)
             reader = _ChunkReader(
-                None, cm, cm.physical_type,
-                max_def=1 if field.nullable else 0,
-                prefetched=(hdrs, dev, dict_raw, (fp, start, size)))
+                None, c.cm, c.cm.physical_type,
+                max_def=1 if c.field.nullable else 0,
+                prefetched=(hdrs, dev, dict_raw, ranges[k]))
             try:
                 prep = reader._prepare_batched(device,
                                                upload_metas=dc is None)
@@ -1115,47 +1250,32 @@ def _read_pieces_impl(my, columns, ctx, direct: bool):
             col = None
             dinfo = None
             if dc is not None:
-                # the pages must be what the footer promised
-                if (prep is None or prep.mode != dc.kind
-                        or prep.total_nv != nrows
-                        or (dc.kind == "dict" and (
-                            prep.dict_vals is None
-                            or prep.dict_vals.dtype != object))):
+                dinfo = _direct_info(dc, prep, c)
+                if dinfo is None:
                     return _RETRY
-                lut = dc.unifier.add(prep.dict_vals) \
-                    if dc.kind == "dict" else None
-                dinfo = (dc, row0, lut)
             elif prep is None:
                 # not eligible for the batched path: the per-chunk route
                 # now, so the chunk does not hold up its group
-                col = reader.decode_column(device, field)
-                done = torch.cuda.Event()
-                done.record()
-                inflight.append((done, 1))
+                col = reader.decode_column(device, c.field)
+                dec.queued(1)
             STATS["t_decode"] = STATS.get("t_decode", 0.0) + \
                 time.perf_counter() - t0
             if prep is None and col is None:
                 return None
-            if name not in metas_of:
-                seen_names.append(name)
-                field_of[name] = field
-            metas_of.setdefault(name, []).append(cm)
-            group.append([name, reader, field, prep, col, dinfo])
-        if not flush():
+            field_of.setdefault(c.name, c.field)
+            metas_of.setdefault(c.name, []).append(c.cm)
+            dec.entries.append(
+                _GroupEntry(c.name, reader, c.field, prep, col, dinfo))
+        if not dec.flush():
             return None
-    finally:
-        with gate:
-            stop[0] = True
-            gate.notify_all()
-        ex.shutdown(wait=True, cancel_futures=True)
     if err is not None and int(err.item()) != 0:  # the read's one sync
         return _RETRY
-    out_names = [n for n in names if n in seen_names]
+    out_names = [n for n in names if n in metas_of]
     out_cols = []
     for n in out_names:
         dc = plan.get(n)
         if dc is None:
-            col = ops.concat_columns(pieces[n])
+            col = ops.concat_columns(dec.pieces[n])
         elif dc.kind == "dict":
             col = Column(bt.dictionary, dc.data,
                          dictionary=dc.unifier.dictionary(),
@@ -1170,27 +1290,17 @@ def _read_pieces_impl(my, columns, ctx, direct: bool):
 
 
 def _read_row_group_gpu(fp: str, rg: int, columns, ctx) -> Optional[Table]:
-    pf = pq.ParquetFile(fp)
-    md = pf.metadata
-    schema = pf.schema_arrow
-    rgm = md.row_group(rg)
-    names = columns or [schema.field(i).name for i in range(len(schema.names))]
+    chunks, names, _ = _scan_chunks([(fp, rg)], columns)
     cols, out_names = [], []
     with open(fp, "rb") as f:
-        for ci in range(rgm.num_columns):
-            cm = rgm.column(ci)
-            cname = cm.path_in_schema
-            if cname not in names:
-                continue
-            phys = cm.physical_type
-            field = schema.field(cname)
-            reader = _ChunkReader(f, cm, phys,
-                                  max_def=1 if field.nullable else 0)
-            col = reader.decode_column(ctx.device, field)
+        for c in chunks:
+            reader = _ChunkReader(f, c.cm, c.cm.physical_type,
+                                  max_def=1 if c.field.nullable else 0)
+            col = reader.decode_column(ctx.device, c.field)
             if col is None:
                 return None
             cols.append(col)
-            out_names.append(cname)
+            out_names.append(c.name)
     ordered = [n for n in names if n in out_names]
     tbl = Table(out_names, cols)
     return tbl.select(ordered)

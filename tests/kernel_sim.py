@@ -223,3 +223,250 @@ def sim_byte_array(scratch, metas, vdo, dense_off, n_valid, dense_total):
         assert pos <= int(pm["dst_len"]) - (voff - int(pm["dst_off"])), \
             f"byte array walk overran page {p}"
     return lengths, src_abs
+
+
+# ---------------------------------------------------------------------
+# kernels that take tables of absolute addresses (pq_decompress_multi,
+# pq_values_multi).  The simulators never touch a raw address: an
+# AddressMap of the tensors the reader allocated turns [addr, addr + n)
+# into (bytes of one tensor, offset), and asserts when the range is not
+# wholly inside one of them.
+# ---------------------------------------------------------------------
+
+PQK_CODES = 0
+PQE_PREFIX = 1
+PQE_LEVELS = 2
+PQE_ENTRY = 4
+PQE_CODES = 8
+PQE_RANGE = 16
+
+
+class AddressMap:
+    """Tensors by address.  Holds them, so no address is handed out twice
+    while the map lives."""
+
+    def __init__(self):
+        self.tensors = {}  # data_ptr -> flat uint8 tensor over its bytes
+
+    def add(self, t: torch.Tensor):
+        assert t.is_contiguous()
+        self.tensors[t.data_ptr()] = t.reshape(-1).view(torch.uint8)
+
+    def find(self, addr: int, n: int):
+        """(base address, bytes) of the tensor holding [addr, addr + n)."""
+        assert n >= 0, f"negative length {n}"
+        for base, t in self.tensors.items():
+            if base <= addr < base + t.numel() or (n == 0 and addr == base):
+                assert addr + n <= base + t.numel(), \
+                    f"[{addr:#x}, +{n}) runs {addr + n - base - t.numel()} " \
+                    f"bytes past its tensor of {t.numel()}"
+                return base, t.numpy()
+        raise AssertionError(f"[{addr:#x}, +{n}) is in no recorded tensor")
+
+    def resolve(self, addr: int, n: int):
+        base, arr = self.find(addr, n)
+        return arr, addr - base
+
+
+def sim_decompress_multi(pages, amap: AddressMap):
+    """pages: PagePtr entries (src, dst, src_len, dst_len, flags)."""
+    for pm in pages:
+        src, so = amap.resolve(int(pm["src"]), int(pm["src_len"]))
+        dst, do = amap.resolve(int(pm["dst"]), int(pm["dst_len"]))
+        sim_decompress(src, [{"src_off": so, "src_len": pm["src_len"],
+                              "dst_off": do, "dst_len": pm["dst_len"],
+                              "flags": pm["flags"]}], dst)
+
+
+def _varint32(b: Buf, pos, end):
+    """pq_varint32: at most 5 bytes inside [pos, end); None when it runs
+    out."""
+    v = 0
+    for shift in range(0, 35, 7):
+        if pos >= end:
+            return None, pos
+        c = b[pos]
+        pos += 1
+        v |= (c & 0x7F) << shift
+        if not (c & 0x80):
+            return v, pos
+    return None, pos
+
+
+def _check_levels(page: Buf, dst_len, nv):
+    """pq_check_levels: (PQE_* bits, offset of the values section)."""
+    if dst_len < 4:
+        return PQE_PREFIX, 4
+    lvl_len = page[0] | (page[1] << 8) | (page[2] << 16) | (page[3] << 24)
+    if lvl_len >= 1 << 31:
+        lvl_len -= 1 << 32
+    if lvl_len < 0 or 4 + lvl_len > dst_len:
+        return PQE_PREFIX, 4 + lvl_len
+    lv = Buf(page.a, page.lo + 4, page.hi)
+    bad, pos, out = 0, 0, 0
+    while out < nv and pos < lvl_len:
+        h, pos = _varint32(lv, pos, lvl_len)
+        if h is None:
+            break
+        if h & 1:  # bit-packed, 1 bit per level
+            groups = h >> 1
+            if pos + groups > lvl_len:
+                break
+            count = min(groups * 8, nv - out)
+            full, rest = count >> 3, count & 7
+            for i in range(full):
+                if lv[pos + i] != 0xFF:
+                    bad = PQE_LEVELS
+            if rest and lv[pos + full] & ((1 << rest) - 1) != (1 << rest) - 1:
+                bad = PQE_LEVELS
+            pos += groups
+        else:
+            count = min(h >> 1, nv - out)
+            if pos >= lvl_len:
+                break
+            if count and lv[pos] != 1:
+                bad = PQE_LEVELS
+            pos += 1
+        out += count
+    if out != nv:
+        bad |= PQE_LEVELS
+    return bad, 4 + lvl_len
+
+
+def _expand_codes_checked(d: Buf, dlen, nval, o, lut, code_lim):
+    """pq_expand_codes_page: d starts at the bit-width byte and may be read
+    up to d.slack bytes past dlen; o is the int32 destination of nval
+    codes.  Returns PQE_CODES / PQE_RANGE bits."""
+    if dlen < 1:
+        return PQE_CODES if nval else 0
+    bitwidth = d[0]
+    d = Buf(d.a, d.lo + 1, d.hi, d.slack)
+    dlen -= 1
+
+    def store(i, c):
+        assert 0 <= i < nval, f"code store at {i} of {nval}"
+        if c < code_lim:
+            o[i] = lut[c] if lut is not None else c
+            return 0
+        return PQE_RANGE
+
+    if bitwidth == 0:
+        if not nval:
+            return 0
+        if not code_lim:
+            return PQE_RANGE
+        o[:nval] = lut[0] if lut is not None else 0
+        return 0
+    if bitwidth > 24:
+        return PQE_CODES
+    wb = (bitwidth + 7) // 8
+    st, pos, outp = 0, 0, 0
+    while outp < nval and pos < dlen:
+        h, pos = _varint32(d, pos, dlen)
+        if h is None:
+            break
+        if h & 1:
+            groups = h >> 1
+            if pos + groups * bitwidth > dlen:
+                break
+            count = min(groups * 8, nval - outp)
+            bitoff = pos * 8
+            for i in range(count):
+                bp = bitoff + i * bitwidth
+                byte = bp >> 3
+                w = (d[byte] | (d[byte + 1] << 8) | (d[byte + 2] << 16)
+                     | (d[byte + 3] << 24))
+                st |= store(outp + i, (w >> (bp & 7)) & ((1 << bitwidth) - 1))
+            pos += groups * bitwidth
+        else:
+            count = min(h >> 1, nval - outp)
+            if pos + wb > dlen:
+                break
+            val = 0
+            for i in range(wb):
+                val |= d[pos + i] << (8 * i)
+            pos += wb
+            val &= 0xFFFFFFFF
+            if val < code_lim:
+                assert outp + count <= nval
+                o[outp:outp + count] = lut[val] if lut is not None else val
+            elif count:
+                st |= PQE_RANGE
+        outp += count
+    if outp < nval:
+        st |= PQE_CODES
+    return st
+
+
+def _fixed_read_span(s, nbytes, out_addr):
+    """[lo, hi) of the addresses pq_copy_fixed_page loads to copy nbytes
+    from address s: aligned u64 words merged by a shift, so it starts at s
+    rounded down to 8 and may take in the word after the last one needed."""
+    m = s & 7
+    lo, hi = s, s + nbytes
+    if out_addr & 7 == 0:
+        nw = nbytes // 8
+        if nw and m:
+            lo, hi = s - m, max(hi, s - m + 8 * (nw + 1))
+        return lo, hi
+    for i in range(max(nbytes // 4 - 2, 0), nbytes // 4):
+        bit = i * 32 + m * 8
+        words = (bit >> 6) + (2 if bit & 63 > 32 else 1)
+        lo, hi = s - m, max(hi, s - m + 8 * words)
+    return lo, hi
+
+
+def sim_values_multi(pages, amap: AddressMap, err: np.ndarray):
+    """pages: ValPage entries; err: int32[1], ORed into.  A page that fails
+    a check is left unwritten (a codes page: from the bad code on, as the
+    kernel), and its PQE_* bits go into err."""
+    for e in pages:
+        kind, out_addr = int(e["kind"]), int(e["out"])
+        dst_len, nv = int(e["dst_len"]), int(e["nv"])
+        codes = kind == PQK_CODES
+        bad, voff = 0, 0
+        if dst_len < 0 or nv < 0:
+            bad = PQE_ENTRY
+        if not codes:
+            if kind not in (4, 8) or out_addr & 3 or \
+                    (kind == 8 and out_addr & 7):
+                bad = PQE_ENTRY
+        elif out_addr & 3:
+            bad = PQE_ENTRY
+        if not bad:
+            base, arr = amap.find(int(e["page"]), dst_len)
+            po = int(e["page"]) - base
+            if int(e["flags"]) & PQF_HAS_DEF:
+                bad, voff = _check_levels(Buf(arr, po, po + dst_len),
+                                          dst_len, nv)
+        if not bad and not codes:
+            nbytes = nv * kind
+            if voff + nbytes > dst_len:
+                bad = PQE_PREFIX
+            else:
+                lo, hi = _fixed_read_span(int(e["page"]) + voff, nbytes,
+                                          out_addr)
+                assert amap.find(lo, hi - lo)[0] == base, \
+                    "word loads leave the page's tensor"
+                vals = sim_copy_fixed(
+                    arr, [{"dst_off": po, "dst_len": dst_len, "nv": nv}],
+                    [voff], [0], None, kind, nv)
+                out, oo = amap.resolve(out_addr, nbytes)
+                out[oo:oo + nbytes] = vals
+        elif not bad:
+            out, oo = amap.resolve(out_addr, nv * 4)
+            code_lim = max(int(e["code_lim"]), 0)
+            lut = None
+            if int(e["lut"]):
+                assert int(e["lut"]) % 4 == 0, "unaligned code table"
+                la, lo = amap.resolve(int(e["lut"]), code_lim * 4)
+                lut = la[lo:lo + code_lim * 4].view(np.int32)
+            # a bit-packed value is read as a 4-byte word that may end up
+            # to 3 bytes past the page: it must still be inside the tensor
+            slack = min(3, len(arr) - (po + dst_len))
+            st = _expand_codes_checked(
+                Buf(arr, po + voff, po + dst_len, slack), dst_len - voff, nv,
+                out[oo:oo + nv * 4].view(np.int32), lut, code_lim)
+            bad |= st
+        if bad:
+            err[0] |= bad
