@@ -8,7 +8,7 @@ eager fallback; round-end native check).
 from __future__ import annotations
 
 import os
-from typing import List, Optional, Sequence, Tuple
+from typing import Callable, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -149,17 +149,18 @@ def gather_string(col: Column, idx: torch.Tensor) -> Column:
 # groupby
 # ----------------------------------------------------------------------
 
-_AGG_OP = {
-    "sum_f64": 0, "sum_i64": 1, "count": 2, "min_f64": 3, "max_f64": 4,
-    "min_i64": 5, "max_i64": 6, "size": 7, "first_row": 8, "last_row": 9,
-    "prod_f64": 10,
-}
-
-# float min/max accumulators start at the identity of the op, so a group
-# whose valid values are all +inf (min) or all -inf (max) keeps them
-_F64_INF = float("inf")
+# op name -> (id in csrc/kernels.hip AggOp, init_f, init_i).  Accumulators
+# start at the identity of the op, so a group whose valid values are all
+# +inf (min) or all -inf (max) keeps them.
 _I64_MAX = int(np.iinfo(np.int64).max)
 _I64_MIN = int(np.iinfo(np.int64).min)
+_AGG_OPS = {
+    "sum_f64": (0, 0.0, 0), "sum_i64": (1, 0.0, 0), "count": (2, 0.0, 0),
+    "min_f64": (3, float("inf"), 0), "max_f64": (4, -float("inf"), 0),
+    "min_i64": (5, 0.0, _I64_MAX), "max_i64": (6, 0.0, _I64_MIN),
+    "size": (7, 0.0, 0), "first_row": (8, 0.0, _I64_MAX),
+    "last_row": (9, 0.0, _I64_MIN), "prod_f64": (10, 1.0, 0),
+}
 
 
 def _keys_valid_mask(cols: Sequence[Column]) -> Optional[torch.Tensor]:
@@ -276,15 +277,12 @@ def slot_digits(slots: torch.Tensor, plan):
 def _groupby_dense(keys, key_cols, batch, plan, n) -> Optional[Table]:
     """Dense route of groupby_local; None when a key lay outside its
     val_range, in which case nothing was computed."""
-    K = kernels()
-    device = key_cols[0].device
-    datas, masks, dtypes, ops_, init_fs, init_is, _, posts = \
-        _fused_specs(batch, {}, device)
-    flat = K.groupby_dense_fused(
+    recs = [_fused_agg(col, func) for _, col, func in batch]
+    flat = kernels().groupby_dense_fused(
         [_data_mask8(c)[0] for c in key_cols],
         [int(c.dtype.kind) for c in key_cols],
         [lo for lo, _ in plan], [radix for _, radix in plan],
-        datas, masks, dtypes, ops_, init_fs, init_is, n)
+        *_fused_args(recs, key_cols[0].device), n)
     if not flat:
         return None
     slots = flat[0]
@@ -296,9 +294,7 @@ def _groupby_dense(keys, key_cols, batch, plan, n) -> Optional[Table]:
                      length=ngroups)
         col.val_range = c.val_range
         out_cols.append(col)
-    results = {}
-    _finish_fused(batch, posts, flat[1:], results)
-    out_cols += [results[o] for o, _, _ in batch]
+    out_cols += _finish_fused(recs, flat[1:])
     return Table(list(keys) + [o for o, _, _ in batch], out_cols, ngroups)
 
 
@@ -333,10 +329,11 @@ def groupby_local(tbl: Table, keys: Sequence[str],
                 n = len(tbl)
     if n == 0:
         return _empty_gb_result(tbl, keys, aggs)
+    # (out_name, column or None, func) per aggregate, for both routes
+    batch = [(o, tbl.column(i) if i and tbl.has_column(i) else None, f)
+             for o, i, f in aggs]
     bounds_hold = True
     if DENSE_GROUPBY:
-        batch = [(o, tbl.column(i) if i and tbl.has_column(i) else None, f)
-                 for o, i, f in aggs]
         plan = dense_groupby_plan(key_cols, batch, n)
         if plan is not None:
             dense = _groupby_dense(keys, key_cols, batch, plan, n)
@@ -348,38 +345,98 @@ def groupby_local(tbl: Table, keys: Sequence[str],
             bounds_hold = False
     row_gid, uniq_rows = groupby_build(key_cols, pack=bounds_hold)
     ngroups = int(uniq_rows.numel())
-    out_names = list(keys)
-    out_cols = [_gather_any(tbl.column(k), uniq_rows) for k in keys]
     # fused path: batch simple aggs (count/size/sum/mean/min/max) into one
     # kernel pass sharing the row_gid read; complex aggs go one-by-one
-    fused_batch = []
     results = {}
-
-    def flush_fused():
-        if not fused_batch:
-            return
-        _run_fused(fused_batch, row_gid, ngroups, results)
-        fused_batch.clear()
-
-    for out_name, in_name, func in aggs:
-        col = tbl.column(in_name) if in_name and tbl.has_column(in_name) else None
+    fused = []
+    for out_name, col, func in batch:
         if func in FUSABLE and (col is None or col.dtype.kind != TypeKind.STRING):
-            fused_batch.append((out_name, col, func))
-            if len(fused_batch) == 4:
-                flush_fused()
+            fused.append((out_name, col, func))
+            if len(fused) == MAX_FUSED_AGGS:
+                results.update(_run_fused(fused, row_gid, ngroups))
+                fused = []
         else:
             results[out_name] = _agg_one(col, row_gid, ngroups, func,
                                          uniq_rows, tbl)
-    flush_fused()
-    for out_name, in_name, func in aggs:
-        out_cols.append(results[out_name])
-        out_names.append(out_name)
-    return Table(out_names, out_cols, ngroups)
+    if fused:
+        results.update(_run_fused(fused, row_gid, ngroups))
+    out_cols = [_gather_any(c, uniq_rows) for c in key_cols]
+    out_cols += [results[o] for o, _, _ in batch]
+    return Table(list(keys) + [o for o, _, _ in batch], out_cols, ngroups)
 
 
-def _run_fused(batch, row_gid, ngroups, results):
-    """Launch one agg_update_fused for up to 4 (out_name, col, func)."""
-    K = kernels()
+class _FusedAgg(NamedTuple):
+    """One aggregate of an agg_update_fused / groupby_dense_fused launch."""
+    op: str                 # key of _AGG_OPS
+    col: Optional[Column]   # column the kernel reads; None for `size`
+    want_count: bool        # the aggregate carries a valid count of its own
+    # (acc, cnt, size count shared by the batch or None) -> result
+    finish: Callable[[torch.Tensor, torch.Tensor, Optional[torch.Tensor]],
+                     Column]
+
+
+def _fused_agg(col: Optional[Column], func: str,
+               shared: bool = False) -> _FusedAgg:
+    """The launch and the finisher of one FUSABLE aggregate.  A mean with
+    ``shared`` set carries no valid count of its own and divides by the
+    size count of its batch."""
+    is_float = col is not None and col.dtype.is_float
+    if func == "size" or col is None or (
+            func == "count" and col.mask is None and not is_float):
+        # count over a non-nullable column == size: no column read
+        return _FusedAgg("size", None, True,
+                         lambda acc, cnt, size: Column(bt.int64, cnt))
+    if func == "count":
+        return _FusedAgg("count", col, True,
+                         lambda acc, cnt, size: Column(bt.int64, cnt))
+    if func == "mean":
+        if shared:
+            return _FusedAgg("sum_f64", col, False, lambda acc, cnt, size:
+                             Column(bt.float64, acc / size.to(torch.float64)))
+        return _FusedAgg("sum_f64", col, True, lambda acc, cnt, size:
+                         Column(bt.float64, acc / cnt.to(torch.float64)))
+    if func == "sum":
+        if is_float:
+            return _FusedAgg("sum_f64", col, True,
+                             lambda acc, cnt, size: Column(bt.float64, acc))
+        # pandas: bool sum -> int64
+        return _FusedAgg("sum_i64", col, False,
+                         lambda acc, cnt, size: Column(bt.int64, acc))
+    if is_float:  # min / max
+        return _FusedAgg(f"{func}_f64", col, True, lambda acc, cnt, size:
+                         _finish_minmax_f64(acc, cnt))
+    return _FusedAgg(f"{func}_i64", col, True, lambda acc, cnt, size:
+                     _finish_minmax_i64(col, acc, cnt))
+
+
+def _fused_args(recs: Sequence[_FusedAgg], device):
+    """(datas, masks, dtypes, ops, init_fs, init_is) of a fused launch."""
+    datas, masks, dtypes = [], [], []
+    for r in recs:
+        if r.col is None:
+            datas.append(torch.zeros(1, dtype=torch.int8, device=device))
+            masks.append(None)
+            dtypes.append(int(TypeKind.INT8))
+        else:
+            data, mask8 = _data_mask8(r.col)
+            datas.append(data)
+            masks.append(mask8)
+            dtypes.append(int(r.col.dtype.kind))
+    ops_, init_fs, init_is = zip(*(_AGG_OPS[r.op] for r in recs))
+    return datas, masks, dtypes, list(ops_), list(init_fs), list(init_is)
+
+
+def _finish_fused(recs: Sequence[_FusedAgg], flat) -> List[Column]:
+    """Results of a fused batch from its flat [acc, cnt] pairs."""
+    size = next((flat[2 * k + 1] for k, r in enumerate(recs)
+                 if r.op == "size"), None)
+    return [r.finish(flat[2 * k], flat[2 * k + 1], size)
+            for k, r in enumerate(recs)]
+
+
+def _run_fused(batch, row_gid, ngroups) -> dict:
+    """One agg_update_fused launch for up to MAX_FUSED_AGGS (out_name, col,
+    func); the results by out_name."""
     # means over provably-NaN-free unmasked float columns can reuse a shared
     # group-size count instead of carrying their own valid-count atomics
     clean_float = {}
@@ -387,112 +444,15 @@ def _run_fused(batch, row_gid, ngroups, results):
         if func == "mean" and col is not None and col.mask is None \
                 and col.dtype.is_float and id(col) not in clean_float:
             clean_float[id(col)] = not bool(torch.isnan(col.data).any().item())
-    share_size = any(clean_float.values()) and any(
-        f == "size" or (f == "count" and c is not None and c.mask is None
-                        and not c.dtype.is_float)
-        for _, c, f in batch)
-    datas, masks, dtypes, ops_, init_fs, init_is, wants, posts = \
-        _fused_specs(batch, clean_float if share_size else {},
-                     row_gid.device)
-    flat = K.agg_update_fused(datas, masks, dtypes, ops_, init_fs, init_is,
-                              wants, row_gid, ngroups)
-    _finish_fused(batch, posts, flat, results)
-
-
-def _fused_specs(batch, shared_mean, device):
-    """Kernel arguments of a fused batch of (out_name, col, func), and per
-    aggregate how `_finish_fused` turns (acc, cnt) into the result.  Means
-    over the columns flagged in ``shared_mean`` (by id) carry no valid count
-    of their own and divide by the batch's size count."""
-    datas, masks, dtypes, ops_, init_fs, init_is, wants, posts = \
-        [], [], [], [], [], [], [], []
-    for out_name, col, func in batch:
-        is_float = col is not None and col.dtype.is_float
-        nullable = col is not None and ((col.mask is not None) or is_float)
-        col_for_data = col
-        if func == "size" or col is None or (
-                func == "count" and col.mask is None and not is_float):
-            # count over a non-nullable column == size: no column read
-            ops_.append(_AGG_OP["size"])
-            init_fs.append(0.0)
-            init_is.append(0)
-            wants.append(1)
-            posts.append(("cnt_i64", None))
-            col_for_data = None
-        elif func == "count":
-            ops_.append(_AGG_OP["count"])
-            init_fs.append(0.0)
-            init_is.append(0)
-            wants.append(1)
-            posts.append(("cnt_i64", None))
-        elif func in ("sum", "mean"):
-            if is_float or func == "mean":
-                ops_.append(_AGG_OP["sum_f64"])
-                init_fs.append(0.0)
-                init_is.append(0)
-                shared = (func == "mean"
-                          and shared_mean.get(id(col), False))
-                wants.append(0 if shared else 1)
-                posts.append(("mean_shared" if shared else
-                              ("mean" if func == "mean" else "acc_f64"), None))
-            else:
-                ops_.append(_AGG_OP["sum_i64"])
-                init_fs.append(0.0)
-                init_is.append(0)
-                wants.append(0)
-                posts.append(("acc_i64", None))
-        else:  # min / max
-            if is_float:
-                ops_.append(_AGG_OP[f"{func}_f64"])
-                init_fs.append(_F64_INF if func == "min" else -_F64_INF)
-                init_is.append(0)
-                wants.append(1)
-                posts.append(("minmax_f64", None))
-            else:
-                ops_.append(_AGG_OP[f"{func}_i64"])
-                init_fs.append(0.0)
-                init_is.append(_I64_MAX if func == "min" else _I64_MIN)
-                wants.append(1)
-                posts.append(("minmax_i64", col))
-        if col_for_data is None:
-            data = torch.zeros(1, dtype=torch.int8, device=device)
-            mask8 = None
-            dtypes.append(int(TypeKind.INT8))
-        else:
-            data, mask8 = _data_mask8(col_for_data)
-            dtypes.append(int(col_for_data.dtype.kind))
-        datas.append(data)
-        masks.append(mask8)
-    return datas, masks, dtypes, ops_, init_fs, init_is, wants, posts
-
-
-def _finish_fused(batch, posts, flat, results):
-    """Results of a fused batch from its flat [acc, cnt] pairs."""
-    shared_cnt = None
-    for k in range(len(batch)):
-        if posts[k][0] == "cnt_i64":
-            shared_cnt = flat[2 * k + 1]
-            break
-    for k, (out_name, col, func) in enumerate(batch):
-        acc, cnt = flat[2 * k], flat[2 * k + 1]
-        kind, extra = posts[k]
-        if kind == "cnt_i64":
-            results[out_name] = Column(bt.int64, cnt)
-        elif kind == "acc_f64":
-            results[out_name] = Column(bt.float64, acc)
-        elif kind == "acc_i64":
-            results[out_name] = Column(bt.int64, acc)
-        elif kind == "mean_shared":
-            results[out_name] = Column(
-                bt.float64, acc / shared_cnt.to(torch.float64))
-        elif kind == "mean" and func == "mean":
-            results[out_name] = Column(bt.float64, acc / cnt.to(torch.float64))
-        elif kind == "mean":
-            results[out_name] = Column(bt.float64, acc)
-        elif kind == "minmax_f64":
-            results[out_name] = _finish_minmax_f64(acc, cnt)
-        else:  # minmax_i64
-            results[out_name] = _finish_minmax_i64(col, acc, cnt)
+    recs = [_fused_agg(col, func) for _, col, func in batch]
+    if any(clean_float.values()) and any(r.op == "size" for r in recs):
+        recs = [_fused_agg(col, func, shared=func == "mean"
+                           and clean_float.get(id(col), False))
+                for _, col, func in batch]
+    flat = kernels().agg_update_fused(
+        *_fused_args(recs, row_gid.device),
+        [int(r.want_count) for r in recs], row_gid, ngroups)
+    return {o: c for (o, _, _), c in zip(batch, _finish_fused(recs, flat))}
 
 
 def _finish_minmax_f64(acc: torch.Tensor, cnt: torch.Tensor) -> Column:
@@ -525,148 +485,147 @@ def _gather_any(col: Column, idx: torch.Tensor) -> Column:
     return gather(col, idx)
 
 
+# ---- one aggregate per launch: agg_update ----
+
+def _agg_launch(op: str, data, mask8, kind, row_gid, ngroups,
+                want_count=False, offsets=None):
+    """[acc] or [acc, cnt] of one agg_update launch with the op's identity."""
+    op_id, init_f, init_i = _AGG_OPS[op]
+    return kernels().agg_update(data, mask8, offsets, int(kind), row_gid,
+                                ngroups, op_id, init_f, init_i, want_count)
+
+
+def _agg_column(op: str, col: Column, row_gid, ngroups, want_count=False):
+    data, mask8 = _data_mask8(col)
+    offsets = col.offsets if col.dtype.kind == TypeKind.STRING else None
+    return _agg_launch(op, data, mask8, col.dtype.kind, row_gid, ngroups,
+                       want_count, offsets)
+
+
+def _agg_rows(op: str, row_gid, ngroups, want_count=False):
+    """An aggregate over row ids only (size, first_row, last_row).  The
+    kernel's loader still reads row i of the column for every op but size,
+    so the stand-in column has a zero for every row."""
+    zeros = torch.zeros(int(row_gid.numel()), dtype=torch.int8,
+                        device=row_gid.device)
+    return _agg_launch(op, zeros, None, TypeKind.INT8, row_gid, ngroups,
+                       want_count)
+
+
+def _power_sums(col: Column, row_gid, ngroups, k: int):
+    """(n, s1, .., sk) as float64: the valid count and the sums of the
+    first k powers of the column per group.  The first launch reads the
+    column in its own type and carries the count; the later ones run over
+    float64 powers with the column's mask."""
+    s1, cnt = _agg_column("sum_f64", col, row_gid, ngroups, want_count=True)
+    x = col.data.to(torch.float64)
+    mask8 = _data_mask8(col)[1]
+    sums, power = [s1], x
+    for _ in range(k - 1):
+        power = power * x
+        sums.append(_agg_launch("sum_f64", power, mask8, TypeKind.FLOAT64,
+                                row_gid, ngroups)[0])
+    return (cnt.to(torch.float64), *sums)
+
+
+def _nan_below(n: torch.Tensor, least: int, x: torch.Tensor) -> torch.Tensor:
+    return torch.where(n < least, torch.full_like(x, float("nan")), x)
+
+
+def _one_count(col, row_gid, ngroups, func, uniq_rows):
+    res = _agg_rows(func, row_gid, ngroups) if col is None else \
+        _agg_column(func, col, row_gid, ngroups)
+    return Column(bt.int64, res[1])
+
+
+def _one_fusable(col, row_gid, ngroups, func, uniq_rows):
+    """sum, mean, min and max launch and finish as they do in a batch."""
+    rec = _fused_agg(col, func)
+    res = _agg_column(rec.op, col, row_gid, ngroups, rec.want_count)
+    return rec.finish(res[0], res[-1], None)
+
+
+def _one_first_last(col, row_gid, ngroups, func, uniq_rows):
+    acc, cnt = _agg_column(f"{func}_row", col, row_gid, ngroups,
+                           want_count=True)
+    has = cnt > 0
+    rows = torch.where(has, acc, uniq_rows[:ngroups] if uniq_rows.numel() >= ngroups else acc)
+    got = _gather_any(col, rows.clamp(min=0))
+    if col.mask is None and not col.dtype.is_float and (~has).any():
+        got = Column(got.dtype, got.data, has.clone(), got.offsets,
+                     got.dictionary, len(got))
+    return got
+
+
+def _one_prod(col, row_gid, ngroups, func, uniq_rows):
+    acc = _agg_column("prod_f64", col, row_gid, ngroups, want_count=True)[0]
+    if col.dtype.is_float:
+        return Column(bt.float64, acc)
+    return Column(bt.int64, acc.to(torch.int64))
+
+
+def _one_var(col, row_gid, ngroups, func, uniq_rows):
+    n, s1, s2 = _power_sums(col, row_gid, ngroups, 2)
+    var = _nan_below(n, 2, (s2 - s1 * s1 / n) / (n - 1))
+    if func == "var":
+        return Column(bt.float64, var)
+    return Column(bt.float64, (var / n if func == "sem" else var).sqrt())
+
+
+def _one_any_all(col, row_gid, ngroups, func, uniq_rows):
+    nz = (col.data != 0).to(torch.int64)
+    acc, cnt = _agg_launch("max_i64" if func == "any" else "min_i64", nz,
+                           _data_mask8(col)[1], TypeKind.INT64, row_gid,
+                           ngroups, want_count=True)
+    default = func == "all"  # empty/all-null group: any=False, all=True
+    return Column(bt.boolean, torch.where(
+        cnt == 0, torch.tensor(default, device=acc.device), acc != 0))
+
+
+def _one_skew(col, row_gid, ngroups, func, uniq_rows):
+    n, s1, s2, s3 = _power_sums(col, row_gid, ngroups, 3)
+    mean = s1 / n
+    m2 = s2 / n - mean * mean
+    m3 = s3 / n - 3 * mean * s2 / n + 2 * mean ** 3
+    # pandas adjusted Fisher-Pearson
+    g = torch.sqrt(n * (n - 1)) / (n - 2) * m3 / m2.clamp(min=0) ** 1.5
+    return Column(bt.float64, _nan_below(n, 3, g))
+
+
+def _one_kurt(col, row_gid, ngroups, func, uniq_rows):
+    n, s1, s2, s3, s4 = _power_sums(col, row_gid, ngroups, 4)
+    mean = s1 / n
+    m2 = s2 / n - mean ** 2
+    m4 = (s4 - 4 * mean * s3 + 6 * mean ** 2 * s2) / n - 3 * mean ** 4
+    # pandas adjusted kurtosis (Fisher, bias-corrected); m2 and m4 are
+    # central moments, already divided by n
+    g2 = m4 / m2.clamp(min=0) ** 2 - 3
+    g = (n - 1) / ((n - 2) * (n - 3)) * ((n + 1) * g2 + 6)
+    return Column(bt.float64, _nan_below(n, 4, g))
+
+
+_AGG_ONE = {
+    "size": _one_count, "count": _one_count,
+    "sum": _one_fusable, "mean": _one_fusable,
+    "min": _one_fusable, "max": _one_fusable,
+    "first": _one_first_last, "last": _one_first_last,
+    "prod": _one_prod,
+    "var": _one_var, "std": _one_var, "sem": _one_var,
+    "any": _one_any_all, "all": _one_any_all,
+    "skew": _one_skew, "kurt": _one_kurt,
+    "median": lambda col, row_gid, ngroups, func, uniq_rows:
+        _median_by_group(col, row_gid, ngroups),
+    "nunique": lambda col, row_gid, ngroups, func, uniq_rows:
+        _nunique_by_group(col, row_gid, ngroups),
+}
+
+
 def _agg_one(col: Optional[Column], row_gid: torch.Tensor, ngroups: int,
              func: str, uniq_rows: torch.Tensor, tbl: Table) -> Column:
-    K = kernels()
-
-    def upd(op, init_f=0.0, init_i=0, want_count=False):
-        if col is None:
-            data, mask = torch.zeros(int(row_gid.numel()), dtype=torch.int8,
-                                     device=row_gid.device), None
-        else:
-            data, mask = _data_mask8(col)
-        offsets = col.offsets if (col is not None and col.dtype.kind == TypeKind.STRING) else None
-        dtype = int(col.dtype.kind) if col is not None else int(TypeKind.INT8)
-        return K.agg_update(data, mask, offsets, dtype, row_gid, ngroups,
-                            _AGG_OP[op], init_f, init_i, want_count)
-
-    if func == "size":
-        (acc, cnt) = upd("size")
-        return Column(bt.int64, cnt)
-    if func == "count":
-        acc, cnt = upd("count")
-        return Column(bt.int64, cnt)
-    is_float = col.dtype.is_float
-    if func == "sum":
-        if is_float:
-            acc, cnt = upd("sum_f64", want_count=True)
-            return Column(bt.float64, acc)
-        acc = upd("sum_i64")[0]
-        if col.dtype.kind == TypeKind.BOOL or col.mask is not None:
-            # pandas: bool sum -> int64; masked int sums become float on
-            # to_pandas path anyway
-            pass
-        return Column(bt.int64, acc)
-    if func in ("min", "max"):
-        if is_float:
-            init = _F64_INF if func == "min" else -_F64_INF
-            acc, cnt = upd(f"{func}_f64", init_f=init, want_count=True)
-            return _finish_minmax_f64(acc, cnt)
-        init = _I64_MAX if func == "min" else _I64_MIN
-        acc, cnt = upd(f"{func}_i64", init_i=init, want_count=True)
-        return _finish_minmax_i64(col, acc, cnt)
-    if func == "mean":
-        acc, cnt = upd("sum_f64", want_count=True)
-        out = acc / cnt.to(torch.float64)
-        return Column(bt.float64, out)
-    if func in ("first", "last"):
-        op = "first_row" if func == "first" else "last_row"
-        init = _I64_MAX if func == "first" else _I64_MIN
-        acc, cnt = upd(op, init_i=init, want_count=True)
-        has = cnt > 0
-        rows = torch.where(has, acc, uniq_rows[:ngroups] if uniq_rows.numel() >= ngroups else acc)
-        got = _gather_any(col, rows.clamp(min=0))
-        if col.mask is None and not is_float and (~has).any():
-            got = Column(got.dtype, got.data, has.clone(), got.offsets,
-                         got.dictionary, len(got))
-        return got
-    if func == "prod":
-        if is_float:
-            acc, cnt = upd("prod_f64", init_f=1.0, want_count=True)
-            return Column(bt.float64, acc)
-        acc, cnt = upd("prod_f64", init_f=1.0, want_count=True)
-        return Column(bt.int64, acc.to(torch.int64))
-    if func in ("var", "std"):
-        acc, cnt = upd("sum_f64", want_count=True)
-        # sum of squares via squared input
-        sq = col.data.to(torch.float64) ** 2
-        acc2 = K.agg_update(sq, _data_mask8(col)[1], None,
-                            int(TypeKind.FLOAT64), row_gid, ngroups,
-                            _AGG_OP["sum_f64"], 0.0, 0, False)[0]
-        c = cnt.to(torch.float64)
-        var = (acc2 - acc * acc / c) / (c - 1)
-        var = torch.where(cnt < 2, torch.full_like(var, float("nan")), var)
-        return Column(bt.float64, var if func == "var" else var.sqrt())
-    if func in ("any", "all"):
-        nz = (col.data != 0).to(torch.int64)
-        mask8 = _data_mask8(col)[1]
-        op = "max_i64" if func == "any" else "min_i64"
-        init = _I64_MIN if func == "any" else _I64_MAX
-        acc, cnt = K.agg_update(nz, mask8, None, int(TypeKind.INT64),
-                                row_gid, ngroups, _AGG_OP[op], 0.0, init,
-                                True)
-        default = func == "all"  # empty/all-null group: any=False, all=True
-        out = torch.where(cnt == 0,
-                          torch.tensor(default, device=acc.device),
-                          acc != 0 if func == "any" else acc != 0)
-        return Column(bt.boolean, out.to(torch.bool))
-    if func == "skew":
-        x = col.data.to(torch.float64)
-        mask8 = _data_mask8(col)[1]
-        s1, cnt = K.agg_update(x, mask8, None, int(TypeKind.FLOAT64),
-                               row_gid, ngroups, _AGG_OP["sum_f64"], 0.0, 0,
-                               True)
-        s2 = K.agg_update(x * x, mask8, None, int(TypeKind.FLOAT64), row_gid,
-                          ngroups, _AGG_OP["sum_f64"], 0.0, 0, False)[0]
-        s3 = K.agg_update(x * x * x, mask8, None, int(TypeKind.FLOAT64),
-                          row_gid, ngroups, _AGG_OP["sum_f64"], 0.0, 0,
-                          False)[0]
-        n = cnt.to(torch.float64)
-        mean = s1 / n
-        m2 = s2 / n - mean * mean
-        m3 = s3 / n - 3 * mean * s2 / n + 2 * mean ** 3
-        # pandas adjusted Fisher-Pearson
-        g = torch.sqrt(n * (n - 1)) / (n - 2) * m3 / m2.clamp(min=0) ** 1.5
-        g = torch.where(n < 3, torch.full_like(g, float("nan")), g)
-        return Column(bt.float64, g)
-    if func == "kurt":
-        x = col.data.to(torch.float64)
-        mask8 = _data_mask8(col)[1]
-        s1, cnt = K.agg_update(x, mask8, None, int(TypeKind.FLOAT64),
-                               row_gid, ngroups, _AGG_OP["sum_f64"], 0.0, 0,
-                               True)
-        s2 = K.agg_update(x * x, mask8, None, int(TypeKind.FLOAT64), row_gid,
-                          ngroups, _AGG_OP["sum_f64"], 0.0, 0, False)[0]
-        s3 = K.agg_update(x * x * x, mask8, None, int(TypeKind.FLOAT64),
-                          row_gid, ngroups, _AGG_OP["sum_f64"], 0.0, 0,
-                          False)[0]
-        s4 = K.agg_update(x * x * x * x, mask8, None, int(TypeKind.FLOAT64),
-                          row_gid, ngroups, _AGG_OP["sum_f64"], 0.0, 0,
-                          False)[0]
-        n = cnt.to(torch.float64)
-        mean = s1 / n
-        m2 = s2 / n - mean ** 2
-        m4 = (s4 - 4 * mean * s3 + 6 * mean ** 2 * s2) / n - 3 * mean ** 4
-        # pandas adjusted kurtosis (Fisher, bias-corrected)
-        g = (n - 1) / ((n - 2) * (n - 3)) * (
-            (n + 1) * (n * m4 / m2.clamp(min=0) ** 2 - 3) + 6)
-        g = torch.where(n < 4, torch.full_like(g, float("nan")), g)
-        return Column(bt.float64, g)
-    if func == "sem":
-        acc, cnt = upd("sum_f64", want_count=True)
-        sq = col.data.to(torch.float64) ** 2
-        mask8 = _data_mask8(col)[1]
-        acc2 = K.agg_update(sq, mask8, None, int(TypeKind.FLOAT64), row_gid,
-                            ngroups, _AGG_OP["sum_f64"], 0.0, 0, False)[0]
-        c = cnt.to(torch.float64)
-        var = (acc2 - acc * acc / c) / (c - 1)
-        var = torch.where(cnt < 2, torch.full_like(var, float("nan")), var)
-        return Column(bt.float64, (var / c).sqrt())
-    if func == "median":
-        return _median_by_group(col, row_gid, ngroups)
-    if func == "nunique":
-        return _nunique_by_group(col, row_gid, ngroups, tbl)
-    raise NotImplementedError(f"gpu agg {func}")
+    """One aggregate outside a fused batch, from its own launches."""
+    if func not in _AGG_ONE:
+        raise NotImplementedError(f"gpu agg {func}")
+    return _AGG_ONE[func](col, row_gid, ngroups, func, uniq_rows)
 
 
 def _median_by_group(col: Column, row_gid: torch.Tensor, ngroups: int) -> Column:
@@ -699,13 +658,11 @@ def _median_by_group(col: Column, row_gid: torch.Tensor, ngroups: int) -> Column
     return Column(bt.float64, med)
 
 
-def _nunique_by_group(col: Column, row_gid: torch.Tensor, ngroups: int,
-                      tbl: Table) -> Column:
+def _nunique_by_group(col: Column, row_gid: torch.Tensor,
+                      ngroups: int) -> Column:
     # distinct (gid, value) pairs via a second hash groupby
-    gid_col = Column(bt.int32, row_gid)
-    pair_gid, pair_rows = _groupby_pairs(gid_col, col)
+    _, rows = groupby_build([Column(bt.int32, row_gid), col])
     # count valid values per group among distinct pairs
-    rows = pair_rows
     g = row_gid[rows].to(torch.int64)
     valid = torch.ones(int(rows.numel()), dtype=torch.bool, device=rows.device)
     if col.mask is not None:
@@ -714,10 +671,6 @@ def _nunique_by_group(col: Column, row_gid: torch.Tensor, ngroups: int,
         valid &= ~torch.isnan(col.data[rows])
     cnt = torch.bincount(g[valid], minlength=ngroups)
     return Column(bt.int64, cnt)
-
-
-def _groupby_pairs(gid_col: Column, col: Column):
-    return groupby_build([gid_col, col])
 
 
 # ----------------------------------------------------------------------
@@ -943,28 +896,15 @@ def distinct_local(tbl: Table, subset=None, keep: str = "first") -> Table:
     if len(tbl) == 0:
         return tbl
     row_gid, uniq_rows = groupby_build(key_cols)
+    ngroups = int(uniq_rows.numel())
     if keep == "first":
         # uniq_rows is the first CLAIMER (race order); recompute true min row
-        K = kernels()
-        acc = K.agg_update(
-            torch.zeros(len(tbl), dtype=torch.int8, device=tbl.device), None,
-            None, int(TypeKind.INT8), row_gid, int(uniq_rows.numel()),
-            _AGG_OP["first_row"], 0.0, _I64_MAX, False)[0]
-        rows = acc
+        rows = _agg_rows("first_row", row_gid, ngroups)[0]
     elif keep == "last":
-        K = kernels()
-        acc = K.agg_update(
-            torch.zeros(len(tbl), dtype=torch.int8, device=tbl.device), None,
-            None, int(TypeKind.INT8), row_gid, int(uniq_rows.numel()),
-            _AGG_OP["last_row"], 0.0, _I64_MIN, False)[0]
-        rows = acc
+        rows = _agg_rows("last_row", row_gid, ngroups)[0]
     elif keep is False:
         # drop every member of any duplicated group
-        K = kernels()
-        cnt = K.agg_update(
-            torch.zeros(len(tbl), dtype=torch.int8, device=tbl.device), None,
-            None, int(TypeKind.INT8), row_gid, int(uniq_rows.numel()),
-            _AGG_OP["size"], 0.0, 0, True)[1]
+        cnt = _agg_rows("size", row_gid, ngroups, want_count=True)[1]
         singles = cnt[row_gid.long()] == 1
         rows = torch.nonzero(singles, as_tuple=False).reshape(-1)
     else:

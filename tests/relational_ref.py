@@ -214,6 +214,19 @@ def canonical_labels(labels):
     return out
 
 
+def np_encode(keys, plan):
+    """slot = sum_k (key_k - lo_k) * stride_k, the last key fastest, in
+    64-bit unsigned arithmetic as groupby_dense_fused_kernel forms it."""
+    slot = np.zeros(len(keys[0]), dtype=np.uint64)
+    stride = 1
+    for key, (lo, radix) in reversed(list(zip(keys, plan))):
+        digit = key.astype(np.int64).view(np.uint64) - np.uint64(lo % 2**64)
+        assert (digit < radix).all()
+        slot += digit * np.uint64(stride)
+        stride *= radix
+    return slot.astype(np.int64), stride
+
+
 def ref_join_pairs(build_keys, probe_keys, how):
     """Reference of ``join_build`` + ``join_probe``.
 

@@ -11,24 +11,12 @@ import torch
 from bodo_amd.core import types as bt
 from bodo_amd.core.column import Column
 from bodo_amd.ops import gpu
+from tests.relational_ref import np_encode
 
 
 # ----------------------------------------------------------------------
 # slot encoding
 # ----------------------------------------------------------------------
-
-def np_encode(keys, plan):
-    """slot = sum_k (key_k - lo_k) * stride_k, the last key fastest, in
-    64-bit unsigned arithmetic as groupby_dense_fused_kernel forms it."""
-    slot = np.zeros(len(keys[0]), dtype=np.uint64)
-    stride = 1
-    for key, (lo, radix) in reversed(list(zip(keys, plan))):
-        digit = key.astype(np.int64).view(np.uint64) - np.uint64(lo % 2**64)
-        assert (digit < radix).all()
-        slot += digit * np.uint64(stride)
-        stride *= radix
-    return slot.astype(np.int64), stride
-
 
 @pytest.mark.parametrize("plan", [
     [(1, 265), (1, 265), (1, 12), (0, 2), (0, 2), (0, 5)],  # the flagship

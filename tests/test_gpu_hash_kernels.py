@@ -368,6 +368,63 @@ def test_groupby_minmax_finishers_fused_and_agg_one():
                                       check_dtype=False, check_exact=True)
 
 
+_MOMENTS = ("var", "std", "sem", "skew", "kurt")
+
+
+def _moments_table():
+    """257 rows in 6 groups: group 0 has no valid value in either column,
+    groups 1 and 2 have exactly 3 and 4, groups 3..5 about 80 rows with a
+    fifth of them null.  f is float64 with NaNs, i a masked int32; the
+    floats are integers over 8, so every power sum up to the fourth is
+    exact and the order of the atomics cannot matter."""
+    from bodo_amd.core.column import Column
+    from bodo_amd.core.table import Table
+
+    rng = np.random.default_rng(64)
+    n = 257
+    k = np.concatenate([np.zeros(5), np.full(6, 1), np.full(6, 2),
+                        rng.integers(3, 6, n - 17)]).astype(np.int64)
+    null = rng.random(n) < 0.2
+    null[k == 0] = True
+    for g, valid in ((1, 3), (2, 4)):
+        rows = np.nonzero(k == g)[0]
+        null[rows[:valid]] = False
+        null[rows[valid:]] = True
+    order = rng.permutation(n)
+    k, null = k[order], null[order]
+    f = rng.integers(-64, 64, n) / 8.0
+    f[null] = np.nan
+    i = rng.integers(-50, 50, n).astype(np.int32)
+    df = pd.DataFrame({"k": k, "f": f, "i": pd.array(i, dtype="Int32")})
+    df.loc[null, "i"] = pd.NA
+    cols = [Column.from_numpy(k), Column.from_numpy(f),
+            Column.from_numpy(i, mask=~null)]
+    return df, Table(["k", "f", "i"], cols, n)
+
+
+def test_groupby_local_moments_vs_pandas():
+    """var, std, sem, skew and kurt through the kernels (no aggregate in
+    the request sends the groupby elsewhere), against pandas at 1e-9."""
+    from bodo_amd.ops import gpu
+
+    df, t = _moments_table()
+    aggs = [(f"{c}_{f}", c, f) for c in ("f", "i") for f in _MOMENTS]
+    got = _sorted(gpu.groupby_local(t.to_device("cuda"), ["k"], aggs)
+                  .to_pandas(), "k")
+    exp = df.groupby("k").agg(**{
+        o: (c, (lambda x: x.kurt()) if f == "kurt" else f)
+        for o, c, f in aggs}).reset_index()
+    assert df.groupby("k")["f"].count().tolist()[:3] == [0, 3, 4]
+    assert exp.loc[1, "f_kurt"] != exp.loc[1, "f_kurt"]      # 3 values: NaN
+    assert exp.loc[2, "i_kurt"] == exp.loc[2, "i_kurt"]      # 4: a number
+    for o, _, _ in aggs:
+        g = got[o].to_numpy(dtype=np.float64, na_value=np.nan)
+        e = exp[o].to_numpy(dtype=np.float64, na_value=np.nan)
+        print(o, "max abs diff", np.nanmax(np.abs(g - e)))
+        np.testing.assert_allclose(g, e, rtol=1e-9, atol=0, equal_nan=True,
+                                   err_msg=o)
+
+
 @pytest.mark.parametrize("op", [8, 9, 10])
 def test_agg_update_fused_rejects_unsupported_ops(op):
     """first_row, last_row and prod_f64 have no fused form: rejected on the
