@@ -156,6 +156,11 @@ def sim_expand_codes(scratch, metas, vdo, dense_off, n_valid, dense_total,
                    int(pm["dst_off"]) + int(pm["dst_len"]), slack)
         nval = int(n_valid[p]) if n_valid is not None else int(pm["nv"])
         o = Buf(out, int(dense_off[p]), int(dense_off[p]) + nval)
+        if start >= int(pm["dst_off"]) + int(pm["dst_len"]):
+            # no codes section: the kernel reads nothing, not even the
+            # bit-width byte
+            assert nval == 0, f"codes short: 0 != {nval}"
+            continue
         bitwidth = base[0]
         d = Buf(scratch, start + 1, int(pm["dst_off"]) + int(pm["dst_len"]),
                 slack)
