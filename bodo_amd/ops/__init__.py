@@ -393,7 +393,12 @@ def partition_indices(hashes: torch.Tensor, nparts: int) -> Tuple[torch.Tensor, 
     perm[counts[:p].sum():counts[:p+1].sum()] belong to partition p."""
     p = torch.remainder(hashes, nparts)
     p = torch.where(p < 0, p + nparts, p)
-    perm = torch.argsort(p, stable=True)
+    from . import gpu
+
+    if gpu.radix_route("partition", p):
+        perm = gpu.radix_argsort(p, 0, max(1, (nparts - 1).bit_length()))
+    else:
+        perm = torch.argsort(p, stable=True)
     counts = torch.bincount(p, minlength=nparts)
     return perm, counts
 
@@ -409,32 +414,50 @@ def sort_indices(cols: Sequence[Column], ascending: Sequence[bool],
     argsort instead of one stable pass per key."""
     device = cols[0].device if cols else torch.device("cpu")
     n = len(cols[0]) if cols else 0
-    packed = pack_ordered_keys(cols, ascending)
+    from . import gpu
+
+    packed, nbits = _pack_ordered_keys_bits(cols, ascending)
     if packed is not None:
+        if gpu.radix_route("packed", packed):
+            return gpu.radix_argsort(packed, 0, nbits)
         return torch.argsort(packed, stable=True)
-    idx = torch.arange(n, dtype=torch.int64, device=device)
+    idx = None  # the identity, until a key has been sorted by
     for c, asc in reversed(list(zip(cols, ascending))):
         keys = _sort_key_tensor(c, asc, na_position)
-        k = keys[idx]
+        if gpu.radix_route("per_key", keys):
+            # reads the keys through idx and carries the row ids itself
+            idx = gpu.radix_argsort(keys, perm=idx)
+            continue
+        k = keys if idx is None else keys[idx]
         order = torch.argsort(k, stable=True)
-        idx = idx[order]
+        idx = order if idx is None else idx[order]
+    if idx is None:
+        idx = torch.arange(n, dtype=torch.int64, device=device)
     return idx
 
 
 def pack_ordered_keys(cols: Sequence[Column],
                       ascending: Sequence[bool]) -> Optional[torch.Tensor]:
+    """The packed key of _pack_ordered_keys_bits without its width."""
+    return _pack_ordered_keys_bits(cols, ascending)[0]
+
+
+def _pack_ordered_keys_bits(cols: Sequence[Column], ascending: Sequence[bool]
+                            ) -> Tuple[Optional[torch.Tensor], int]:
     """Pack sort keys into one int64 whose numeric order equals the
     lexicographic (keys, ascending) order.  First key occupies the most
     significant bits; DICT codes are rank-remapped by dictionary value
     order; descending keys are bit-flipped within their range.  Returns
-    None when any key is unsuitable (mask, float, wide range, strings)."""
+    (None, 0) when any key is unsuitable (mask, float, wide range, strings);
+    otherwise (packed, nbits), every packed value below 2**nbits, nbits the
+    sum of the keys' field widths (at most 63)."""
     if not cols:
-        return None
+        return None, 0
     widths = []
     parts = []
     for c, asc in zip(cols, ascending):
         if c.mask is not None:
-            return None
+            return None, 0
         k = c.dtype.kind
         if k == TypeKind.DICT:
             import pyarrow.compute as pc
@@ -451,7 +474,7 @@ def pack_ordered_keys(cols: Sequence[Column],
             lo, hi = c.val_range
             vals = c.data.long()
         else:
-            return None
+            return None, 0
         width = max(1, int(hi - lo + 1).bit_length())
         v = vals - lo
         if not asc:
@@ -459,11 +482,11 @@ def pack_ordered_keys(cols: Sequence[Column],
         parts.append(v)
         widths.append(width)
     if sum(widths) > 63:
-        return None
+        return None, 0
     packed = None
     for v, w in zip(parts, widths):
         packed = v if packed is None else ((packed << w) | v)
-    return packed
+    return packed, sum(widths)
 
 
 def _sort_key_tensor(c: Column, asc: bool, na_position: str) -> torch.Tensor:

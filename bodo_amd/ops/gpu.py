@@ -927,6 +927,44 @@ def _empty_gb_result(tbl: Table, keys, aggs) -> Table:
     return T(names, cols, 0)
 
 
+# Radix argsort (csrc/sort.hip): a stable LSD radix sort that is told which
+# key bits matter and reads its first pass through an incoming permutation.
+# BODO_AMD_RADIX_SORT=0 turns the route off; =force turns it on for every
+# class of use, also those that RADIX_SORT_CLASSES leaves with torch because
+# they did not beat it when measured (profiles/radix_sort.md).
+RADIX_SORT = os.environ.get("BODO_AMD_RADIX_SORT", "1") != "0"
+RADIX_SORT_FORCE = os.environ.get("BODO_AMD_RADIX_SORT", "1") == "force"
+RADIX_SORT_CLASSES = {"packed": False, "per_key": False, "partition": True}
+RADIX_SORT_MIN_ROWS = 0
+_RADIX_DTYPES = (torch.int8, torch.int16, torch.int32, torch.int64,
+                 torch.uint8, torch.bool, torch.float32, torch.float64)
+
+
+def radix_route(cls: str, keys: torch.Tensor) -> bool:
+    """Whether an ordering of class `cls` ("packed", "per_key",
+    "partition") over `keys` goes to radix_argsort."""
+    return (RADIX_SORT and keys.is_cuda
+            and (RADIX_SORT_FORCE or RADIX_SORT_CLASSES[cls])
+            and keys.dtype in _RADIX_DTYPES
+            and RADIX_SORT_MIN_ROWS <= keys.numel() < 2 ** 31)
+
+
+def radix_argsort(keys: torch.Tensor, begin_bit: int = 0,
+                  end_bit: Optional[int] = None,
+                  perm: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """p[argsort(K[p], stable=True)] as int64, where K is `keys` restricted
+    to bits [begin_bit, end_bit) of its order-preserving unsigned form
+    (end_bit None: the dtype's width) and p is `perm` or the identity."""
+    if keys.dtype == torch.bool:
+        keys = keys.view(torch.uint8)
+    n = keys.numel() if perm is None else perm.numel()
+    if max(n, keys.numel()) >= 2 ** 31:
+        raise ValueError("radix_argsort takes fewer than 2^31 rows")
+    return kernels().radix_argsort(
+        keys.contiguous(), begin_bit, -1 if end_bit is None else end_bit,
+        None if perm is None else perm.contiguous())
+
+
 def take_table_fused(tbl: Table, idx: torch.Tensor) -> Optional[Table]:
     """All fixed-width columns (+masks) of a take materialize in ONE kernel
     launch (join-heavy queries were launch-bound on per-column

@@ -167,7 +167,12 @@ def shuffle_table(tbl: Table, part_ids: torch.Tensor) -> Table:
         return tbl
     from .. import ops
 
-    perm = torch.argsort(part_ids, stable=True)
+    from ..ops import gpu
+
+    if gpu.radix_route("partition", part_ids):
+        perm = gpu.radix_argsort(part_ids, 0, max(1, (w - 1).bit_length()))
+    else:
+        perm = torch.argsort(part_ids, stable=True)
     counts = torch.bincount(part_ids, minlength=w)
     packed = ops.take_table(tbl, perm)
     str_idx = [i for i, c in enumerate(packed.columns)

@@ -1500,6 +1500,13 @@ torch::Tensor pq_parse_headers(torch::Tensor chunk_buf);
 std::vector<torch::Tensor> gather_multi(std::vector<torch::Tensor> srcs,
                                         torch::Tensor idx);
 
+// sort.hip: stable LSD radix argsort over a caller-given key bit range
+torch::Tensor radix_argsort(torch::Tensor keys, int64_t begin_bit,
+                            int64_t end_bit,
+                            c10::optional<torch::Tensor> perm,
+                            int64_t max_blocks);
+int64_t radix_tile();
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_f32", &gemm_f32, "f32 MFMA GEMM (v_mfma_f32_16x16x4_f32)");
   m.def("rle_expand", &rle_expand, "parquet RLE/bit-packed hybrid expand");
@@ -1543,5 +1550,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "host-side thrift page-header parse of a chunk buffer");
   m.def("gather_multi", &gather_multi,
         "fused multi-column fixed-width gather (one launch per table)");
+  m.def("radix_argsort", &radix_argsort,
+        "stable radix argsort of key bits [begin_bit, end_bit), optionally "
+        "through an incoming permutation",
+        py::arg("keys"), py::arg("begin_bit") = 0, py::arg("end_bit") = -1,
+        py::arg("perm") = py::none(), py::arg("max_blocks") = 2048);
+  m.attr("RADIX_TILE") = radix_tile();
   m.attr("_native") = true;
 }
