@@ -719,6 +719,15 @@ _NSLOTS = int(os.environ.get("BODO_AMD_READ_THREADS", "12"))
 # chunk takes the per-chunk finish and the pieces are concatenated)
 DIRECT = os.environ.get("BODO_AMD_PQ_DIRECT", "1") != "0"
 
+# run a group's decode kernels on the extension's decode stream, under the
+# chunk uploads of the next group (off: on the current stream, after them)
+DECODE_STREAM = os.environ.get("BODO_AMD_PQ_DECODE_STREAM", "1") != "0"
+
+
+def _decode_stream_on(device) -> bool:
+    """Streams exist on the GPU only; the CPU tests put a stand-in here."""
+    return DECODE_STREAM and torch.device(device).type == "cuda"
+
 _DICT_ENCODINGS = {"RLE_DICTIONARY", "PLAIN_DICTIONARY"}
 _DIRECT_PLAIN = {"INT32": torch.int32, "INT64": torch.int64,
                  "FLOAT": torch.float32, "DOUBLE": torch.float64}
@@ -1093,6 +1102,13 @@ def _read_pieces_pipelined(my, columns, ctx) -> Optional[Table]:
     ops.concat_columns.  Integer and date32 columns get val_range from the
     footer's min/max on both routes.
 
+    On the GPU a group's kernels run on the extension's decode stream
+    (K.pq_decode_group; BODO_AMD_PQ_DECODE_STREAM=0 turns it off), ordered
+    after the group's uploads, so that they run under the uploads of the
+    next group.  The current stream joins that stream before it finishes a
+    chunk that is not direct, and before the read ends on any path
+    (profiles/decode_stream.md).
+
     Disk read overlaps PCIe upload and decode kernels of other chunks
     (reference role: bodo/io/parquet_reader.cpp prefetch +
     _io_cpu_thread_pool.cpp)."""
@@ -1117,6 +1133,9 @@ class _GroupDecoder:
         # (event, chunk count) per flushed group or per-chunk fallback decode
         self.inflight: list = []
         self.pieces: dict = {}  # name -> Columns of the non-direct chunks
+        # groups decode on the decode stream (K.pq_decode_group)
+        self.side = _decode_stream_on(device)
+        self.done = None  # the last group's event there, until it is joined
 
     def queued(self, n_chunks: int) -> None:
         """n_chunks more chunks were just queued on the current stream."""
@@ -1126,11 +1145,30 @@ class _GroupDecoder:
         """Backpressure: keep at most ~2x the slot depth of decoded chunks
         in flight on the GPU (unbounded enqueue ran the allocator far ahead
         of execution on 600+-chunk shards); the group being prepared
-        counts, flushed work is waited for."""
-        while self.inflight and (sum(c for _, c in self.inflight)
-                                 + len(self.entries) >= limit):
+        counts, flushed work is waited for.  A group on the decode stream
+        is meant to run while the next one's uploads are queued, so there
+        the newest flushed group is not waited for: what is not yet decoded
+        is at most that group and the one being collected."""
+        keep = 1 if self.side else 0
+        while len(self.inflight) > keep and (
+                sum(c for _, c in self.inflight) + len(self.entries) >= limit):
             done, _ = self.inflight.pop(0)
             _wait_event(done)
+
+    def join(self) -> None:
+        """The current stream waits for every group on the decode stream:
+        they run there in order, so for the last one."""
+        if self.done is not None:
+            import bodo_amd_kernels as K
+
+            K.pq_decode_join(self.done)
+            self.done = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.join()
 
     def flush(self) -> bool:
         """One decompress launch for every prepared chunk of the group and
@@ -1144,19 +1182,36 @@ class _GroupDecoder:
         t0 = time.perf_counter()
         preps = [e.prep for e in self.entries if e.prep is not None]
         directs = [e for e in self.entries if e.direct is not None]
+        done = None  # the group's event on the decode stream
         if preps:
             tables = _GroupTables(preps, directs)
             blob = torch.empty(tables.nbytes, dtype=torch.uint8,
                                device=self.device)
             _upload_staged(_TABLE_STAGING, tables.fill(blob.data_ptr()), blob)
-            K.pq_decompress_multi(blob[:tables.dec_bytes], tables.n_dec)
-            if tables.n_val:
-                K.pq_values_multi(
-                    blob[tables.dec_bytes:tables.dec_bytes + tables.val_bytes],
-                    tables.n_val, self.err)
+            if self.side:
+                done = self.done = K.pq_decode_group(
+                    blob, tables.dec_bytes, tables.n_dec, tables.val_bytes,
+                    tables.n_val, self.err, self._group_tensors(blob, preps,
+                                                                directs))
+                if len(directs) < len(preps):
+                    # _finish reads such a chunk's scratch on the current
+                    # stream: it has to wait, and this group's decode does
+                    # not run under the next one's uploads
+                    self.join()
+            else:
+                K.pq_decompress_multi(blob[:tables.dec_bytes], tables.n_dec)
+                if tables.n_val:
+                    K.pq_values_multi(
+                        blob[tables.dec_bytes:
+                             tables.dec_bytes + tables.val_bytes],
+                        tables.n_val, self.err)
         for e in self.entries:
             self._finish(e)
-        if preps:
+        if done is not None:
+            # back-pressure by the decode itself: its chunk buffers are
+            # held until then
+            self.inflight.append((done, len(preps)))
+        elif preps:
             self.queued(len(preps))
         STATS["t_decode"] = STATS.get("t_decode", 0.0) + \
             time.perf_counter() - t0
@@ -1170,6 +1225,19 @@ class _GroupDecoder:
             self.pieces.setdefault(e.name, []).append(e.column)
         self.entries, self.row_groups = [], 0
         return ok
+
+    def _group_tensors(self, blob: torch.Tensor, preps: List[_Prepared],
+                       directs: List[_GroupEntry]) -> List[torch.Tensor]:
+        """Every device tensor the group's kernels touch: the decode stream
+        has to be recorded on each before the reader lets go of it."""
+        out = [blob]
+        for p in preps:
+            out += [p.src_dev, p.scratch]
+        cols = {id(e.direct.col): e.direct.col.data for e in directs}
+        out += cols.values()
+        if self.err is not None:
+            out.append(self.err)
+        return out
 
     def _finish(self, e: _GroupEntry) -> None:
         """After the group's launches: count a direct chunk, decode the
@@ -1220,7 +1288,9 @@ def _read_pieces_impl(my, columns, ctx, direct: bool):
     field_of: dict = {}
     group_rgs, n_slots = _GROUP_ROW_GROUPS, _NSLOTS
     ranges = [(c.path, c.start, c.size) for c in chunks]
-    with _Prefetcher(ranges, n_slots, device) as pf:
+    # leaving dec joins the decode stream, on the early ways out as well: no
+    # decode is still to run when the read's tensors are dropped
+    with dec, _Prefetcher(ranges, n_slots, device) as pf:
         for k, c in enumerate(chunks):
             if c.first_of_rg:
                 if dec.row_groups >= group_rgs and not dec.flush():

@@ -18,9 +18,11 @@
 #include <c10/hip/HIPStream.h>
 
 #include <cstring>
+#include <memory>
 #include <vector>
 
 #include "common.h"
+#include "parquet.h"
 
 #define CHECK_HIP(x)                                                    \
   do {                                                                  \
@@ -1473,6 +1475,12 @@ void pq_decompress(torch::Tensor src, torch::Tensor pages_blob,
 void pq_decompress_multi(torch::Tensor pages_blob, int64_t n_pages);
 void pq_values_multi(torch::Tensor pages_blob, int64_t n_pages,
                      torch::Tensor err);
+std::shared_ptr<PqDone> pq_decode_group(torch::Tensor blob, int64_t dec_bytes,
+                                        int64_t n_dec, int64_t val_bytes,
+                                        int64_t n_val,
+                                        c10::optional<torch::Tensor> err,
+                                        std::vector<torch::Tensor> tensors);
+void pq_decode_join(std::shared_ptr<PqDone> done);
 std::vector<torch::Tensor> pq_def_levels(torch::Tensor scratch,
                                          torch::Tensor pages_blob,
                                          int64_t n_pages, int64_t bitwidth,
@@ -1536,6 +1544,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "snappy decompress over a table of absolute page addresses");
   m.def("pq_values_multi", &pq_values_multi,
         "checked PLAIN / dictionary-code pages of a group -> shard columns");
+  py::class_<PqDone, std::shared_ptr<PqDone>>(m, "PqDone")
+      .def("synchronize", &PqDone::synchronize,
+           py::call_guard<py::gil_scoped_release>())
+      .def("query", &PqDone::query);
+  m.def("pq_decode_group", &pq_decode_group,
+        "a group's decompress and values launches on the decode stream, "
+        "after the current stream's work so far; returns its done event");
+  m.def("pq_decode_join", &pq_decode_join,
+        "the current stream waits for a pq_decode_group event");
   m.def("pq_def_levels", &pq_def_levels,
         "definition levels -> validity mask + per-page valid counts");
   m.def("pq_expand_codes", &pq_expand_codes,

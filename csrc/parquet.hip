@@ -24,12 +24,18 @@
 
 #include <torch/extension.h>
 #include <ATen/ATen.h>
+#include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
+#include <c10/hip/HIPCachingAllocator.h>
+#include <c10/hip/HIPGuard.h>
 #include <c10/hip/HIPStream.h>
 
 #include <cstring>
+#include <memory>
+#include <mutex>
 #include <vector>
 
 #include "common.h"
+#include "parquet.h"
 
 #define CHECK_HIP_PQ(x)                                                 \
   do {                                                                  \
@@ -843,43 +849,170 @@ void pq_decompress(torch::Tensor src, torch::Tensor pages_blob,
   CHECK_HIP_PQ(hipGetLastError());
 }
 
-// pages_blob: device bytes of n_pages PagePtr entries (absolute device
-// addresses).  The caller keeps the tensors they point into alive.
-void pq_decompress_multi(torch::Tensor pages_blob, int64_t n_pages) {
+// The two group launchers: argument checks and launches on the stream they
+// are given.  pages: device bytes of n_pages table entries.
+
+static void pq_launch_decompress_multi(const void* pages, int64_t avail,
+                                       int64_t n_pages, hipStream_t stream) {
   if (!n_pages) return;
-  TORCH_CHECK(pages_blob.is_contiguous() &&
-                  pages_blob.numel() * pages_blob.element_size() >=
-                      n_pages * (int64_t)sizeof(PagePtr),
+  TORCH_CHECK(avail >= n_pages * (int64_t)sizeof(PagePtr),
               "pq_decompress_multi: page table too small");
   hipLaunchKernelGGL(pq_decompress_multi_kernel,
-                     dim3(pq_grid_pages(n_pages)), dim3(WAVE), 0, pq_stream(),
-                     (const PagePtr*)pages_blob.data_ptr(), (int)n_pages);
+                     dim3(pq_grid_pages(n_pages)), dim3(WAVE), 0, stream,
+                     (const PagePtr*)pages, (int)n_pages);
   CHECK_HIP_PQ(hipGetLastError());
 }
 
-// pages_blob: device bytes of n_pages ValPage entries; err: one int32 on
-// the device, ORed into.  Two launches whatever the table holds: PLAIN
-// pages one block each, codes pages one wave each.
-void pq_values_multi(torch::Tensor pages_blob, int64_t n_pages,
-                     torch::Tensor err) {
+// Two launches whatever the table holds: PLAIN pages one block each, codes
+// pages one wave each.
+static void pq_launch_values_multi(const void* pages, int64_t avail,
+                                   int64_t n_pages, const torch::Tensor& err,
+                                   const torch::Device& dev,
+                                   hipStream_t stream) {
   if (!n_pages) return;
-  TORCH_CHECK(pages_blob.is_contiguous() &&
-                  pages_blob.numel() * pages_blob.element_size() >=
-                      n_pages * (int64_t)sizeof(ValPage),
+  TORCH_CHECK(avail >= n_pages * (int64_t)sizeof(ValPage),
               "pq_values_multi: page table too small");
   TORCH_CHECK(n_pages < (1ll << 31), "pq_values_multi: too many pages");
   TORCH_CHECK(err.scalar_type() == torch::kInt32 && err.numel() >= 1 &&
-                  err.device() == pages_blob.device(),
+                  err.device() == dev,
               "pq_values_multi: err must be an int32 on the table's device");
   int grid = (int)std::min<int64_t>(n_pages, 1 << 16);
   hipLaunchKernelGGL(pq_values_multi_kernel<false>, dim3(grid), dim3(256), 0,
-                     pq_stream(), (const ValPage*)pages_blob.data_ptr(),
-                     (int)n_pages, (int32_t*)err.data_ptr());
+                     stream, (const ValPage*)pages, (int)n_pages,
+                     (int32_t*)err.data_ptr());
   CHECK_HIP_PQ(hipGetLastError());
   hipLaunchKernelGGL(pq_values_multi_kernel<true>, dim3(grid), dim3(WAVE), 0,
-                     pq_stream(), (const ValPage*)pages_blob.data_ptr(),
-                     (int)n_pages, (int32_t*)err.data_ptr());
+                     stream, (const ValPage*)pages, (int)n_pages,
+                     (int32_t*)err.data_ptr());
   CHECK_HIP_PQ(hipGetLastError());
+}
+
+// pages_blob: device bytes of n_pages PagePtr entries (absolute device
+// addresses).  The caller keeps the tensors they point into alive.
+void pq_decompress_multi(torch::Tensor pages_blob, int64_t n_pages) {
+  TORCH_CHECK(pages_blob.is_contiguous(),
+              "pq_decompress_multi: page table too small");
+  pq_launch_decompress_multi(pages_blob.data_ptr(),
+                             pages_blob.numel() * pages_blob.element_size(),
+                             n_pages, pq_stream());
+}
+
+// pages_blob: device bytes of n_pages ValPage entries; err: one int32 on
+// the device, ORed into.
+void pq_values_multi(torch::Tensor pages_blob, int64_t n_pages,
+                     torch::Tensor err) {
+  TORCH_CHECK(pages_blob.is_contiguous(),
+              "pq_values_multi: page table too small");
+  pq_launch_values_multi(pages_blob.data_ptr(),
+                         pages_blob.numel() * pages_blob.element_size(),
+                         n_pages, err, pages_blob.device(), pq_stream());
+}
+
+// ---------------------------------------------------------------------
+// a group's decode on the decode stream
+//
+// The chunk uploads of the next group are copies on the current stream;
+// the decode of this group is kernels.  On one stream they run one after
+// the other.  pq_decode_group puts a group's three launches on a stream of
+// the extension's own, ordered after everything queued so far on the
+// current stream, so that they run under the uploads that follow.
+// ---------------------------------------------------------------------
+
+PqDone::PqDone(int device) : device(device) {
+  CHECK_HIP_PQ(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+}
+
+PqDone::~PqDone() { (void)hipEventDestroy(ev); }
+
+void PqDone::synchronize() { CHECK_HIP_PQ(hipEventSynchronize(ev)); }
+
+bool PqDone::query() {
+  hipError_t e = hipEventQuery(ev);
+  if (e == hipErrorNotReady) return false;
+  CHECK_HIP_PQ(e);
+  return true;
+}
+
+namespace {
+
+struct PqDecodeStream {
+  c10::hip::HIPStream stream;
+  hipEvent_t ready;  // "the group's uploads are queued": re-recorded per group
+};
+
+// One per device, made at the first group decoded there.  The stream comes
+// from PyTorch's pool (default priority, non-blocking) so that the caching
+// allocator's recordStream knows it.
+PqDecodeStream& pq_decode_stream(c10::DeviceIndex device) {
+  static std::mutex mu;
+  static std::vector<std::unique_ptr<PqDecodeStream>> streams;
+  std::lock_guard<std::mutex> lock(mu);
+  if ((size_t)device >= streams.size()) streams.resize(device + 1);
+  if (!streams[device]) {
+    hipEvent_t ready;
+    CHECK_HIP_PQ(hipEventCreateWithFlags(&ready, hipEventDisableTiming));
+    streams[device].reset(new PqDecodeStream{
+        c10::hip::getStreamFromPoolMasqueradingAsCUDA(
+            /*isHighPriority=*/false, device).hip_stream(), ready});
+  }
+  return *streams[device];
+}
+
+}  // namespace
+
+// blob: the group's table blob on the device: n_dec PagePtr entries in its
+// first dec_bytes, then n_val ValPage entries in val_bytes.  tensors: every
+// device tensor the tables point into, and blob and err themselves.  They
+// are marked as used by the decode stream, so the caller may drop them as
+// soon as the call returns: the allocator hands their memory out again only
+// after the decode.  Returns the event that marks the group decoded.
+std::shared_ptr<PqDone> pq_decode_group(torch::Tensor blob, int64_t dec_bytes,
+                                        int64_t n_dec, int64_t val_bytes,
+                                        int64_t n_val,
+                                        c10::optional<torch::Tensor> err,
+                                        std::vector<torch::Tensor> tensors) {
+  TORCH_CHECK(blob.is_cuda() && blob.is_contiguous() &&
+                  blob.scalar_type() == torch::kUInt8,
+              "pq_decode_group: blob must be device bytes");
+  TORCH_CHECK(dec_bytes >= 0 && val_bytes >= 0 && dec_bytes % 8 == 0 &&
+                  dec_bytes + val_bytes <= blob.numel(),
+              "pq_decode_group: tables outside the blob");
+  TORCH_CHECK(!n_val || err.has_value(),
+              "pq_decode_group: values pages need an error word");
+  auto dev = blob.device();
+  for (const auto& t : tensors)
+    TORCH_CHECK(t.device() == dev,
+                "pq_decode_group: a tensor is not on the blob's device");
+  c10::hip::HIPGuard guard(dev.index());
+  PqDecodeStream& ds = pq_decode_stream(dev.index());
+  hipStream_t side = ds.stream.stream();
+
+  // after the group's last chunk upload and the table upload
+  CHECK_HIP_PQ(hipEventRecord(
+      ds.ready, c10::hip::getCurrentHIPStream(dev.index()).stream()));
+  CHECK_HIP_PQ(hipStreamWaitEvent(side, ds.ready, 0));
+
+  const uint8_t* base = (const uint8_t*)blob.data_ptr();
+  pq_launch_decompress_multi(base, dec_bytes, n_dec, side);
+  if (n_val)
+    pq_launch_values_multi(base + dec_bytes, val_bytes, n_val, *err, dev,
+                           side);
+
+  for (const auto& t : tensors)
+    c10::hip::HIPCachingAllocator::recordStream(t.storage().data_ptr(),
+                                                ds.stream);
+  auto done = std::make_shared<PqDone>((int)dev.index());
+  CHECK_HIP_PQ(hipEventRecord(done->ev, side));
+  return done;
+}
+
+// The current stream waits for a group decoded by pq_decode_group.
+void pq_decode_join(std::shared_ptr<PqDone> done) {
+  TORCH_CHECK(done != nullptr, "pq_decode_join: no event");
+  c10::hip::HIPGuard guard((c10::DeviceIndex)done->device);
+  CHECK_HIP_PQ(hipStreamWaitEvent(
+      c10::hip::getCurrentHIPStream((c10::DeviceIndex)done->device).stream(),
+      done->ev, 0));
 }
 
 std::vector<torch::Tensor> pq_def_levels(torch::Tensor scratch,
