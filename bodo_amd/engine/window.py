@@ -136,11 +136,14 @@ def _ordered_local_device(tbl: Table, keys, order_by, ascending,
     bodo/libs/window/_window_calculator.cpp:2106, redesigned as whole-shard
     tensor passes instead of chunked streaming)."""
     from ..core.types import TypeKind as TK
+    from ..ops import gpu
 
     n = len(tbl)
     dev = tbl.device
     if n == 0:
         return None
+    # running and rolling frames as segmented scans (csrc/window.hip)
+    use_scan = gpu.SEG_SCAN and torch.device(dev).type == "cuda"
     key_cols = [tbl.column(k) for k in keys]
     order_cols = [tbl.column(c) for c in order_by]
     asc = list(ascending) or [True] * len(order_by)
@@ -150,7 +153,7 @@ def _ordered_local_device(tbl: Table, keys, order_by, ascending,
         if func in ("first_value_ig", "last_value_ig"):
             return None  # ignore-nulls variants: host path
         if func.startswith("rolling_") and func[8:] in ("min", "max") \
-                and int(arg or 1) > _ROLLING_MINMAX_CAP:
+                and int(arg or 1) > _ROLLING_MINMAX_CAP and not use_scan:
             return None
         if in_name and tbl.has_column(in_name):
             ic = tbl.column(in_name)
@@ -194,6 +197,12 @@ def _ordered_local_device(tbl: Table, keys, order_by, ascending,
         cs = torch.cumsum(vf.double() if vf.dtype != torch.float64 else vf, 0)
         excl = cs - (vf.double() if vf.dtype != torch.float64 else vf)
         return cs - excl[seg_start]
+
+    def seg_scan(name, op, heads=seg_new, **kw):
+        v, inv = sorted_vals(name)
+        if v.dtype not in gpu.SEG_SCAN_DTYPES:
+            v = v.double() if v.dtype.is_floating_point else v.long()
+        return gpu.segmented_scan(v, heads, op, inv, **kw), inv
 
     out_sorted = {}
     for out_name, in_name, func, arg in specs:
@@ -254,6 +263,54 @@ def _ordered_local_device(tbl: Table, keys, order_by, ascending,
                 res = res[r_inv][idx]
                 if res_inv is not None:
                     res_inv = res_inv[r_inv][idx]
+        elif func == "cumsum" and use_scan:
+            exact = tbl.column(in_name).dtype.is_integer and \
+                tbl.column(in_name).mask is None
+            res, res_inv = seg_scan(in_name, "sum_i64" if exact else "sum_f64")
+        elif func in ("cummin", "cummax", "cummean", "cumcount_v") \
+                and use_scan:
+            op = {"cummin": "min_f64", "cummax": "max_f64"}.get(func, "sum_f64")
+            (res, cnt), _ = seg_scan(in_name, op, want_count=True)
+            res_inv = cnt == 0
+            if func == "cummean":
+                res = res / cnt.double()
+            elif func == "cumcount_v":
+                res, res_inv = cnt, None
+        elif func.startswith("rolling_") and use_scan and (
+                func[8:] not in ("min", "max")
+                or int(arg) >= gpu.SEG_SCAN_ROLLING_MINMAX_MIN_WIDTH):
+            base = func[len("rolling_"):]
+            w = int(arg)
+            if base in ("sum", "mean", "count"):
+                # frame = running value at i minus the one before the frame;
+                # both belong to this partition
+                (cs, cv), _ = seg_scan(in_name, "sum_f64", want_count=True)
+                lo = torch.maximum(pos - (w - 1), seg_start)
+                cut = lo > seg_start
+                before = (lo - 1).clamp(min=0)
+                rsum = cs - torch.where(cut, cs[before],
+                                        torch.zeros((), dtype=cs.dtype,
+                                                    device=dev))
+                rcount = cv - torch.where(cut, cv[before],
+                                          torch.zeros((), dtype=cv.dtype,
+                                                      device=dev))
+                res = {"sum": rsum, "count": rcount.double(),
+                       "mean": rsum / rcount.double()}[base]
+                res_inv = rcount == 0 if base != "count" else None
+            else:
+                # van Herk / Gil-Werman: chunks of w rows from each
+                # partition's start, a forward and a reverse scan over them,
+                # and a frame is the tail of one chunk and the head of the
+                # next
+                chunks = row_in_seg % w == 0
+                op = base + "_f64"
+                (fwd, fc), _ = seg_scan(in_name, op, chunks, want_count=True)
+                (rev, rc), _ = seg_scan(in_name, op, chunks, want_count=True,
+                                        reverse=True)
+                res, res_inv = gpu.kernels().seg_window_combine(
+                    fwd, rev, fc, rc, row_in_seg.contiguous(), w,
+                    base == "max")
+                res_inv = res_inv.bool()
         elif func == "cumsum":
             v, inv = sorted_vals(in_name, fill0=True)
             res = seg_cumsum(v)

@@ -965,6 +965,36 @@ def radix_argsort(keys: torch.Tensor, begin_bit: int = 0,
         None if perm is None else perm.contiguous())
 
 
+# Segmented scan (csrc/window.hip): running and rolling window frames over
+# head-flagged partitions.  BODO_AMD_SEG_SCAN=0 sends engine/window.py back
+# to its whole-tensor torch passes.
+SEG_SCAN = os.environ.get("BODO_AMD_SEG_SCAN", "1") != "0"
+# rolling min/max narrower than this stays on the torch shift loop, whose
+# width - 1 passes were faster when measured (profiles/seg_scan.md)
+SEG_SCAN_ROLLING_MINMAX_MIN_WIDTH = 4
+SEG_SCAN_OPS = {"sum_f64": 0, "sum_i64": 1, "min_f64": 2, "max_f64": 3}
+SEG_SCAN_DTYPES = (torch.int8, torch.int16, torch.int32, torch.int64,
+                   torch.uint8, torch.bool, torch.float32, torch.float64)
+
+
+def segmented_scan(values: torch.Tensor, heads: torch.Tensor, op: str,
+                   invalid: Optional[torch.Tensor] = None,
+                   reverse: bool = False, want_count: bool = False):
+    """Inclusive scan of `values` under `op` (a key of SEG_SCAN_OPS) that
+    restarts at every row whose `heads` flag is set; rows flagged `invalid`
+    contribute nothing.  reverse scans each segment from its last row.
+    Returns acc, or (acc, running count of valid rows) with want_count."""
+    def u8(x):
+        return (x.view(torch.uint8) if x.dtype == torch.bool else x).contiguous()
+
+    if values.numel() >= 2 ** 31:
+        raise ValueError("segmented_scan takes fewer than 2^31 rows")
+    out = kernels().seg_scan(
+        u8(values), None if invalid is None else u8(invalid), u8(heads),
+        SEG_SCAN_OPS[op], reverse, want_count)
+    return tuple(out) if want_count else out[0]
+
+
 def take_table_fused(tbl: Table, idx: torch.Tensor) -> Optional[Table]:
     """All fixed-width columns (+masks) of a take materialize in ONE kernel
     launch (join-heavy queries were launch-bound on per-column

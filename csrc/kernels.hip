@@ -1515,6 +1515,17 @@ torch::Tensor radix_argsort(torch::Tensor keys, int64_t begin_bit,
                             int64_t max_blocks);
 int64_t radix_tile();
 
+// window.hip: segmented scan over head-flagged rows, rolling min/max finish
+std::vector<torch::Tensor> seg_scan(torch::Tensor values,
+                                    c10::optional<torch::Tensor> invalid,
+                                    torch::Tensor heads, int64_t op,
+                                    bool reverse, bool want_count,
+                                    int64_t max_blocks);
+std::vector<torch::Tensor> seg_window_combine(
+    torch::Tensor P, torch::Tensor S, torch::Tensor pc, torch::Tensor sc,
+    torch::Tensor row_in_seg, int64_t w, bool is_max);
+int64_t seg_scan_tile();
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_f32", &gemm_f32, "f32 MFMA GEMM (v_mfma_f32_16x16x4_f32)");
   m.def("rle_expand", &rle_expand, "parquet RLE/bit-packed hybrid expand");
@@ -1573,5 +1584,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("keys"), py::arg("begin_bit") = 0, py::arg("end_bit") = -1,
         py::arg("perm") = py::none(), py::arg("max_blocks") = 2048);
   m.attr("RADIX_TILE") = radix_tile();
+  m.def("seg_scan", &seg_scan,
+        "segmented inclusive scan (op 0 SUM_F64, 1 SUM_I64, 2 MIN_F64, "
+        "3 MAX_F64) of values over head-flagged segments -> [acc] or "
+        "[acc, count of valid rows]",
+        py::arg("values"), py::arg("invalid"), py::arg("heads"),
+        py::arg("op"), py::arg("reverse") = false,
+        py::arg("want_count") = false, py::arg("max_blocks") = 2048);
+  m.def("seg_window_combine", &seg_window_combine,
+        "rolling min/max of width w from the forward and reverse chunk "
+        "scans -> [value, invalid]");
+  m.attr("SEG_SCAN_TILE") = seg_scan_tile();
   m.attr("_native") = true;
 }
