@@ -64,6 +64,10 @@ KERNEL_CACHE_DIR = os.environ.get(
     "BODO_AMD_KERNEL_CACHE",
     os.path.join(os.path.expanduser("~"), ".cache", "bodo_amd_kernels"))
 
+#: LIKE / contains / startswith / endswith on plain string columns run the
+#: gfx950 kernel of csrc/strmatch.hip on a GPU; off = arrow compute on host
+STRING_MATCH = _env_bool("BODO_AMD_STRING_MATCH", True)
+
 
 def default_device() -> str:
     if DEVICE:

@@ -1099,6 +1099,36 @@ def _str_dict_generic(a: Column, op: str, args, kwargs) -> Column:
     return Column(bt.float64, lut[a.data.long()], a.mask)
 
 
+def _like_regex(pattern: str) -> str:
+    """RE2 source of a LIKE pattern without '_': '%' is any run of
+    characters, line feeds included."""
+    import re
+
+    from .gpu import like_segments
+
+    segs, anchor_start, anchor_end = like_segments(pattern)
+    return ("(?s)^" + ("" if anchor_start else ".*")
+            + ".*".join(re.escape(s.decode()) for s in segs)
+            + ("" if anchor_end else ".*") + "$")
+
+
+def _device_string_match(a: Column, op: str, pat: str) -> Optional[Column]:
+    """contains / startswith / endswith / like on a plain string column as
+    one csrc/strmatch.hip launch; None when the pattern is more than the
+    kernel takes in its arguments."""
+    from . import gpu
+
+    if op == "like":
+        segs, anchor_start, anchor_end = gpu.like_segments(pat)
+    else:
+        segs = [pat.encode()] if pat else []
+        anchor_start, anchor_end = op == "startswith", op == "endswith"
+    if not gpu.string_match_eligible(segs):
+        return None
+    out = gpu.string_match(a, segs, anchor_start, anchor_end)
+    return Column(bt.boolean, out, a.mask)
+
+
 def str_op(a: Column, op: str, args, kwargs=None) -> Column:
     import pyarrow.compute as pc
 
@@ -1142,7 +1172,7 @@ def str_op(a: Column, op: str, args, kwargs=None) -> Column:
                               length=len(a))
             return Column(a.dtype, a.data, a.mask, dictionary=nd, length=len(a))
         if op in ("contains", "contains_re", "match", "match_full",
-                  "startswith", "endswith", "count_re", "len"):
+                  "startswith", "endswith", "like", "count_re", "len"):
             if op == "count_re":
                 lut_np = pc.count_substring_regex(
                     d, args[0]).to_numpy(zero_copy_only=False).astype(np.int64)
@@ -1159,13 +1189,23 @@ def str_op(a: Column, op: str, args, kwargs=None) -> Column:
                      "match_full": lambda x: pc.match_substring_regex(
                          x, "^(?:" + pat + ")$"),
                      "startswith": lambda x: pc.starts_with(x, pat),
-                     "endswith": lambda x: pc.ends_with(x, pat)}[op]
+                     "endswith": lambda x: pc.ends_with(x, pat),
+                     "like": lambda x: pc.match_substring_regex(
+                         x, _like_regex(pat))}[op]
                 lut_np = f(d).to_numpy(zero_copy_only=False).astype(bool)
                 ret = bt.boolean
             lut = torch.from_numpy(lut_np).to(a.device)
             out = lut[a.data.long()]
             return Column(ret, out, a.mask)
         return _str_dict_generic(a, op, args, kwargs)
+    from .. import config
+
+    if op in ("contains", "startswith", "endswith", "like") and a.is_cuda \
+            and a.dtype.kind == TypeKind.STRING and config.STRING_MATCH:
+        # on the device; a pattern past the kernel's limits stays below
+        out = _device_string_match(a, op, args[0])
+        if out is not None:
+            return out
     # plain strings: arrow compute on host
     arr = a.to_arrow() if not a.is_cuda else a.to_device("cpu").to_arrow()
     fmap = {
@@ -1178,6 +1218,7 @@ def str_op(a: Column, op: str, args, kwargs=None) -> Column:
         "match": lambda x: pc.match_substring_regex(x, "^" + args[0]),
         "startswith": lambda x: pc.starts_with(x, args[0]),
         "endswith": lambda x: pc.ends_with(x, args[0]),
+        "like": lambda x: pc.match_substring_regex(x, _like_regex(args[0])),
         "title": lambda x: pc.utf8_title(x),
         "capitalize": lambda x: pc.utf8_capitalize(x),
         "slice": lambda x: pc.utf8_slice_codeunits(x, *args),

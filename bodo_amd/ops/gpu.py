@@ -995,6 +995,58 @@ def segmented_scan(values: torch.Tensor, heads: torch.Tensor, op: str,
     return tuple(out) if want_count else out[0]
 
 
+# LIKE on plain string columns (csrc/strmatch.hip).  The kernel takes the
+# pattern in its arguments: up to 8 literal segments, 256 bytes in all.
+STRMATCH_MAX_SEGMENTS = 8
+STRMATCH_MAX_PATTERN_BYTES = 256
+
+
+def like_segments(pattern: str):
+    """A SQL LIKE pattern without '_' as (literal segments as bytes,
+    anchor_start, anchor_end).  '%' separates the segments and empty ones
+    drop out, so 'a%%b' is 'a%b'; a side without a leading / trailing '%' is
+    anchored."""
+    segs = [s.encode() for s in pattern.split("%") if s]
+    return segs, not pattern.startswith("%"), not pattern.endswith("%")
+
+
+def string_match_eligible(segments) -> bool:
+    return len(segments) <= STRMATCH_MAX_SEGMENTS and \
+        sum(map(len, segments)) <= STRMATCH_MAX_PATTERN_BYTES
+
+
+def string_match(col: Column, segments, anchor_start: bool, anchor_end: bool,
+                 max_blocks: int = 2048) -> torch.Tensor:
+    """Bool tensor: row matches the segments in order, without overlap, any
+    bytes between them; False at null rows.  `col` is a plain string column
+    on a GPU and `segments` passes string_match_eligible."""
+    if col.dtype.kind != TypeKind.STRING or not col.is_cuda:
+        raise ValueError("string_match takes a plain string column on a GPU")
+    segments = [bytes(s) for s in segments if len(s)]
+    if not string_match_eligible(segments):
+        raise ValueError(
+            f"string_match takes at most {STRMATCH_MAX_SEGMENTS} segments and "
+            f"{STRMATCH_MAX_PATTERN_BYTES} pattern bytes")
+    if not segments:
+        # nothing for the kernel: '%' matches every row, '' the empty ones
+        if anchor_start and anchor_end:
+            out = col.offsets[1:] == col.offsets[:-1]
+        else:
+            out = torch.ones(len(col), dtype=torch.bool, device=col.device)
+        return out if col.mask is None else out & col.mask
+    data, mask8 = _data_mask8(col)
+    if data is None:
+        data = torch.zeros(0, dtype=torch.uint8, device=col.device)
+    ends = np.cumsum([len(s) for s in segments]).astype(np.int32)
+    out = kernels().string_match(
+        data.contiguous(), col.offsets.contiguous(),
+        None if mask8 is None else mask8.contiguous(),
+        torch.frombuffer(bytearray(b"".join(segments)), dtype=torch.uint8),
+        torch.from_numpy(ends), bool(anchor_start), bool(anchor_end),
+        max_blocks)
+    return out.view(torch.bool)
+
+
 def take_table_fused(tbl: Table, idx: torch.Tensor) -> Optional[Table]:
     """All fixed-width columns (+masks) of a take materialize in ONE kernel
     launch (join-heavy queries were launch-bound on per-column

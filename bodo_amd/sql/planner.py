@@ -2062,6 +2062,9 @@ def _like_expr(operand: ex.Expr, pattern: str) -> ex.Expr:
         if pattern.startswith("%"):
             return ex.StrOp(operand, "endswith", (body,))
         return ex.Cmp("eq", operand, ex.Const(pattern, bt.string))
+    if "_" not in pattern:
+        # several '%': literal segments in order, matched by str_op "like"
+        return ex.StrOp(operand, "like", (pattern,))
     import re as _re
 
     rx = _re.escape(pattern).replace("%", ".*").replace("_", ".")

@@ -1526,6 +1526,14 @@ std::vector<torch::Tensor> seg_window_combine(
     torch::Tensor row_in_seg, int64_t w, bool is_max);
 int64_t seg_scan_tile();
 
+// strmatch.hip: '%'-separated literal segments on a plain string column
+torch::Tensor string_match(torch::Tensor bytes, torch::Tensor offsets,
+                           c10::optional<torch::Tensor> mask,
+                           torch::Tensor segs, torch::Tensor seg_ends,
+                           bool anchor_start, bool anchor_end,
+                           int64_t max_blocks);
+int64_t strmatch_lds_bytes();
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_f32", &gemm_f32, "f32 MFMA GEMM (v_mfma_f32_16x16x4_f32)");
   m.def("rle_expand", &rle_expand, "parquet RLE/bit-packed hybrid expand");
@@ -1595,5 +1603,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "rolling min/max of width w from the forward and reverse chunk "
         "scans -> [value, invalid]");
   m.attr("SEG_SCAN_TILE") = seg_scan_tile();
+  m.def("string_match", &string_match,
+        "LIKE on a plain string column: segs (host uint8) holds the literal "
+        "segments end to end, seg_ends (host int32) where each one ends -> "
+        "uint8[n], 0 where mask is 0",
+        py::arg("bytes"), py::arg("offsets"), py::arg("mask"),
+        py::arg("segs"), py::arg("seg_ends"), py::arg("anchor_start"),
+        py::arg("anchor_end"), py::arg("max_blocks") = 2048);
+  m.attr("STRMATCH_LDS_BYTES") = strmatch_lds_bytes();
   m.attr("_native") = true;
 }
