@@ -68,6 +68,11 @@ KERNEL_CACHE_DIR = os.environ.get(
 #: gfx950 kernel of csrc/strmatch.hip on a GPU; off = arrow compute on host
 STRING_MATCH = _env_bool("BODO_AMD_STRING_MATCH", True)
 
+#: Limit(Sort) finds its k rows with the radix select of csrc/select.hip on
+#: a GPU ("0": a full sort, then the first k); ops/gpu.py reads the same
+#: variable into TOPK_SELECT, which is what the route consults
+TOPK_SELECT = os.environ.get("BODO_AMD_TOPK_SELECT", "1") != "0"
+
 
 def default_device() -> str:
     if DEVICE:

@@ -379,14 +379,33 @@ def _exec_limit(node: pn.Limit, ctx) -> Table:
     # top-k and resolves globally on rank-replicated candidates — no
     # range-partition exchange of the full table (reference analog: TopN,
     # bodo/pandas/plan.py LogicalTopN:474)
+    # On one GPU the same plan skips the full sort and the full-width
+    # gather: ops.topk_indices finds the offset + n rows by radix select.
+    if isinstance(node.child, pn.Sort) and not node.tail and \
+            node.n > 0 and node.offset >= 0 and \
+            node.offset + node.n <= _TOPK_MAX and ctx.world == 1:
+        from . import ooc
+
+        srt = node.child
+        child = _exec(srt.child, ctx)
+        asc = list(srt.ascending) or [True] * len(srt.keys)
+        budget = ooc.budget_bytes(child.device)
+        if srt.keys and (budget is None or child.nbytes() <= budget):
+            cols = [child.column(k) for k in srt.keys]
+            idx = ops.topk_indices(cols, asc, srt.na_position,
+                                   node.offset + node.n)
+            return ops.take_table(child, idx[node.offset:])
+        # over the device budget: the sort that splits into staged runs
+        child = ooc.sort_local(child, list(srt.keys), asc, srt.na_position)
+        return ops.slice_table(child, node.offset, node.offset + node.n)
     if isinstance(node.child, pn.Sort) and not node.tail and \
             node.offset == 0 and 0 < node.n <= _TOPK_MAX and ctx.world > 1:
         srt = node.child
         child = _exec(srt.child, ctx)
         asc = list(srt.ascending) or [True] * len(srt.keys)
         cols = [child.column(k) for k in srt.keys]
-        idx = ops.sort_indices(cols, asc, srt.na_position)
-        local_top = ops.take_table(child, idx[:node.n])
+        idx = ops.topk_indices(cols, asc, srt.na_position, node.n)
+        local_top = ops.take_table(child, idx)
         full = comm.allgather_table(local_top)
         cols = [full.column(k) for k in srt.keys]
         idx = ops.sort_indices(cols, asc, srt.na_position)

@@ -436,6 +436,47 @@ def sort_indices(cols: Sequence[Column], ascending: Sequence[bool],
     return idx
 
 
+def topk_indices(cols: Sequence[Column], ascending: Sequence[bool],
+                 na_position: str, k: int) -> torch.Tensor:
+    """sort_indices(cols, ascending, na_position)[:k], element for element.
+    Where gpu.topk_route allows, a radix select finds the k rows (with
+    several unpacked keys: every row that ties with the k-th on the first
+    key) and only those candidates are sorted.  They come in row order, so
+    the stable sort breaks ties as the full sort does."""
+    from . import gpu
+
+    k = max(0, int(k))
+    if not cols or not cols[0].is_cuda or \
+            not gpu.topk_shape_route(len(cols[0]), k) or \
+            cols[0].dtype.kind == TypeKind.STRING:
+        return sort_indices(cols, ascending, na_position)[:k]
+    packed, nbits = _pack_ordered_keys_bits(cols, ascending)
+    if packed is not None:
+        if not gpu.topk_route(packed, k):
+            return sort_indices(cols, ascending, na_position)[:k]
+        cand = gpu.radix_select(packed, k, 0, nbits)
+        sub = packed[cand]
+        order = gpu.radix_argsort(sub, 0, nbits) \
+            if gpu.radix_route("packed", sub) \
+            else torch.argsort(sub, stable=True)
+        return cand[order]
+    first = _sort_key_tensor(cols[0], ascending[0], na_position)
+    if not gpu.topk_route(first, k):
+        return sort_indices(cols, ascending, na_position)[:k]
+    if len(cols) == 1:
+        cand = gpu.radix_select(first, k)
+    else:
+        # more ties than this and the candidates' sort is no longer small
+        # next to the full one
+        most = max(k, int(len(first) * gpu.TOPK_SELECT_MAX_CANDIDATES))
+        cand = gpu.radix_select(first, k, ties="all", max_out=most)
+        if cand is None:
+            return sort_indices(cols, ascending, na_position)[:k]
+    order = sort_indices([gather(c, cand) for c in cols], ascending,
+                         na_position)
+    return cand[order[:k]]
+
+
 def pack_ordered_keys(cols: Sequence[Column],
                       ascending: Sequence[bool]) -> Optional[torch.Tensor]:
     """The packed key of _pack_ordered_keys_bits without its width."""

@@ -965,6 +965,56 @@ def radix_argsort(keys: torch.Tensor, begin_bit: int = 0,
         None if perm is None else perm.contiguous())
 
 
+# Radix select (csrc/select.hip): the rows of the k smallest keys without
+# ordering the rest, for Limit(Sort).  BODO_AMD_TOPK_SELECT=0 sends every
+# top-k back to a full sort_indices.  The constants come from
+# profiles/topk_select.md: whole calls on 2^20 and 2^22 rows did not beat
+# the sort route by more than their own spread, and no k above n/16 nor a
+# candidate set above n/16 was measured to win.
+TOPK_SELECT = os.environ.get("BODO_AMD_TOPK_SELECT", "1") != "0"
+TOPK_SELECT_MIN_ROWS = 1 << 24
+TOPK_SELECT_MAX_FRACTION = 1 / 16  # largest routed k / n
+TOPK_SELECT_MAX_CANDIDATES = 1 / 16  # largest sorted share of n (ties="all")
+
+
+def topk_shape_route(n: int, k: int) -> bool:
+    """topk_route's conditions on the row count and k alone."""
+    return (TOPK_SELECT and TOPK_SELECT_MIN_ROWS <= n < 2 ** 31
+            and 0 < k < n and k <= n * TOPK_SELECT_MAX_FRACTION)
+
+
+def topk_route(keys: torch.Tensor, k: int) -> bool:
+    """Whether the k smallest of `keys` are found by radix_select."""
+    return (keys.is_cuda and keys.dtype in _RADIX_DTYPES
+            and topk_shape_route(keys.numel(), k))
+
+
+def radix_select(keys: torch.Tensor, k: int, begin_bit: int = 0,
+                 end_bit: Optional[int] = None, ties: str = "first",
+                 max_out: Optional[int] = None,
+                 max_blocks: int = 2048) -> Optional[torch.Tensor]:
+    """Ascending int64 row ids of the k smallest keys, where K is `keys`
+    restricted to bits [begin_bit, end_bit) of its order-preserving unsigned
+    form and o = argsort(K, stable=True).  ties="first": sort(o[:k]), with
+    no host synchronisation.  ties="all": every row with K <= K[o[k-1]], or
+    None when they are more than `max_out`."""
+    if ties not in ("first", "all"):
+        raise ValueError(f"radix_select: ties must be 'first' or 'all', "
+                         f"not {ties!r}")
+    if keys.dtype == torch.bool:
+        keys = keys.view(torch.uint8)
+    n = keys.numel()
+    if n >= 2 ** 31:
+        raise ValueError("radix_select takes fewer than 2^31 rows")
+    if k <= 0 or n == 0:
+        return torch.empty(0, dtype=torch.int64, device=keys.device)
+    if k >= n:
+        return torch.arange(n, dtype=torch.int64, device=keys.device)
+    return kernels().radix_select(
+        keys.contiguous(), k, begin_bit, -1 if end_bit is None else end_bit,
+        ties == "all", -1 if max_out is None else max_out, max_blocks)
+
+
 # Segmented scan (csrc/window.hip): running and rolling window frames over
 # head-flagged partitions.  BODO_AMD_SEG_SCAN=0 sends engine/window.py back
 # to its whole-tensor torch passes.

@@ -1515,6 +1515,13 @@ torch::Tensor radix_argsort(torch::Tensor keys, int64_t begin_bit,
                             int64_t max_blocks);
 int64_t radix_tile();
 
+// select.hip: row ids of the k smallest keys, in row order
+c10::optional<torch::Tensor> radix_select(torch::Tensor keys, int64_t k,
+                                          int64_t begin_bit, int64_t end_bit,
+                                          bool ties_all, int64_t max_out,
+                                          int64_t max_blocks);
+int64_t select_capacity(int64_t n);
+
 // window.hip: segmented scan over head-flagged rows, rolling min/max finish
 std::vector<torch::Tensor> seg_scan(torch::Tensor values,
                                     c10::optional<torch::Tensor> invalid,
@@ -1592,6 +1599,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("keys"), py::arg("begin_bit") = 0, py::arg("end_bit") = -1,
         py::arg("perm") = py::none(), py::arg("max_blocks") = 2048);
   m.attr("RADIX_TILE") = radix_tile();
+  m.def("radix_select", &radix_select,
+        "ascending row ids of the k smallest keys (1 <= k < n) over key bits "
+        "[begin_bit, end_bit); ties_all: every row at or below the k-th key, "
+        "None when they are more than max_out",
+        py::arg("keys"), py::arg("k"), py::arg("begin_bit") = 0,
+        py::arg("end_bit") = -1, py::arg("ties_all") = false,
+        py::arg("max_out") = -1, py::arg("max_blocks") = 2048);
+  m.def("select_capacity", &select_capacity,
+        "keys the survivor buffer of radix_select holds for n rows");
   m.def("seg_scan", &seg_scan,
         "segmented inclusive scan (op 0 SUM_F64, 1 SUM_I64, 2 MIN_F64, "
         "3 MAX_F64) of values over head-flagged segments -> [acc] or "

@@ -25,7 +25,7 @@
 
 #include <algorithm>
 
-#include "common.h"
+#include "radix.h"
 
 #define CHECK_HIP_SORT(x)                                               \
   do {                                                                  \
@@ -33,46 +33,9 @@
     TORCH_CHECK(e == hipSuccess, "HIP error: ", hipGetErrorString(e));  \
   } while (0)
 
-#define RS_THREADS 256
-#define RS_WAVES (RS_THREADS / WAVE)
-// keys per thread per tile: 8 keeps the scatter kernel at zero scratch and
-// its LDS (tile of keys + ids + counters) at 30 KiB, five blocks per CU
-#define RS_KPT 8
-#define RS_TILE (RS_THREADS * RS_KPT)
-#define RS_BINS 256
-#define RS_MAX_BLOCKS 2048
 #define RS_SCAN_THREADS 1024
 
-// source dtypes of radix_keys_kernel
-enum RadixKind : int {
-  RK_I8 = 0, RK_I16, RK_I32, RK_I64, RK_U8, RK_F32, RK_F64,
-};
-
 // ---------------------------------------------------------------- keys
-
-// u64 whose unsigned order is torch.argsort's order of the source value
-DEV_INLINE uint64_t radix_norm(const void* src, int kind, int64_t i) {
-  switch (kind) {
-    case RK_I8: return (uint8_t)(((const uint8_t*)src)[i] ^ 0x80u);
-    case RK_I16: return (uint16_t)(((const uint16_t*)src)[i] ^ 0x8000u);
-    case RK_I32: return ((const uint32_t*)src)[i] ^ 0x80000000u;
-    case RK_I64: return ((const uint64_t*)src)[i] ^ 0x8000000000000000ULL;
-    case RK_U8: return ((const uint8_t*)src)[i];
-    case RK_F32: {
-      uint32_t b = ((const uint32_t*)src)[i];
-      if ((b & 0x7FFFFFFFu) > 0x7F800000u) return 0xFFFFFFFFu;  // NaN last
-      if (b == 0x80000000u) b = 0;                              // -0.0
-      return (b & 0x80000000u) ? (uint32_t)~b : (b | 0x80000000u);
-    }
-    case RK_F64: {
-      uint64_t b = ((const uint64_t*)src)[i];
-      if ((b & 0x7FFFFFFFFFFFFFFFULL) > 0x7FF0000000000000ULL) return ~0ULL;
-      if (b == 0x8000000000000000ULL) b = 0;
-      return (b & 0x8000000000000000ULL) ? ~b : (b | 0x8000000000000000ULL);
-    }
-  }
-  return 0;
-}
 
 // keys[i] = norm(src[perm ? perm[i] : i]), ids[i] = perm ? perm[i] : i.
 // A perm entry outside [0, n_src) reads nothing and sorts last.
@@ -86,50 +49,6 @@ __global__ __launch_bounds__(RS_THREADS) void radix_keys_kernel(
     keys[i] = ok ? radix_norm(src, kind, r) : ~0ULL;
     ids[i] = (uint32_t)r;
   }
-}
-
-// ---------------------------------------------------------------- helpers
-
-struct RadixRange {
-  int64_t begin, end;  // key positions [begin, end) owned by this block
-};
-
-// block b of nblocks owns a contiguous run of whole tiles; the first
-// (tiles % nblocks) blocks own one tile more
-DEV_INLINE RadixRange radix_block_range(int64_t n, int64_t tiles, int nblocks,
-                                        int b) {
-  int64_t per = tiles / nblocks, rem = tiles % nblocks;
-  int64_t t0 = b * per + (b < rem ? b : rem);
-  int64_t t1 = t0 + per + (b < rem ? 1 : 0);
-  RadixRange r;
-  r.begin = t0 * RS_TILE;
-  r.end = t1 * RS_TILE < n ? t1 * RS_TILE : n;
-  return r;
-}
-
-DEV_INLINE uint32_t radix_digit(uint64_t key, int shift, uint32_t dmask) {
-  return (uint32_t)(key >> shift) & dmask;
-}
-
-// lanes of this wave that are valid and hold the same digit as the caller;
-// one ballot per digit bit.  Every lane of the wave must call it.
-DEV_INLINE uint64_t radix_peers(uint32_t d, int nbits, bool valid) {
-  uint64_t peers = __ballot(valid);
-  for (int b = 0; b < nbits; ++b) {
-    bool bit = (d >> b) & 1u;
-    uint64_t m = __ballot(bit);
-    peers &= bit ? m : ~m;
-  }
-  return peers;
-}
-
-DEV_INLINE uint32_t wave_incl_scan(uint32_t v, int lane) {
-#pragma unroll
-  for (int off = 1; off < WAVE; off <<= 1) {
-    uint32_t t = __shfl_up(v, off);
-    if (lane >= off) v += t;
-  }
-  return v;
 }
 
 // ---------------------------------------------------------------- count

@@ -17,7 +17,8 @@ setup(
         CUDAExtension(
             name="bodo_amd_kernels",
             sources=["csrc/kernels.hip", "csrc/gemm.hip", "csrc/parquet.hip",
-                     "csrc/sort.hip", "csrc/window.hip", "csrc/strmatch.hip"],
+                     "csrc/sort.hip", "csrc/window.hip", "csrc/strmatch.hip",
+                     "csrc/select.hip"],
             extra_compile_args={
                 "cxx": ["-O3", "-std=c++17"],
                 "nvcc": ["-O3", "-std=c++17", "--offload-arch=gfx950"],
