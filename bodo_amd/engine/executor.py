@@ -187,7 +187,8 @@ def _exec_aggregate(node: pn.Aggregate, ctx) -> Table:
 
     if ctx.world == 1:
         return ooc.groupby_local(child, keys, aggs, node.dropna)
-    if any(a[2] in SINGLE_PHASE_AGGS or callable(a[2]) for a in aggs):
+    if any(a[2] in SINGLE_PHASE_AGGS or callable(a[2])
+           or isinstance(a[2], pn.QuantileAgg) for a in aggs):
         # shuffle raw rows by key hash, then single local groupby
         shuffled = _shuffle_by_keys(child, keys, ctx)
         return ooc.groupby_local(shuffled, keys, aggs, node.dropna)
@@ -1067,9 +1068,9 @@ def _finish_reduce(node: pn.Reduce, ctx, partials: dict) -> Table:
 
 
 def _combine_reduce(partials: List[dict], func: str):
-    if callable(func):
+    if callable(func) or isinstance(func, pn.QuantileAgg):
         ser = pd.Series([v for p in partials for v in p["vals_list"]])
-        return func(ser)
+        return func(ser) if callable(func) else func.of_series(ser)
     if func in ("sum",):
         return sum(p["sum"] for p in partials)
     if func in ("count", "size"):

@@ -17,6 +17,7 @@ from ..core import types as bt
 from ..core.column import Column
 from ..core.table import Table
 from ..core.types import TypeKind
+from ..plan.nodes import QuantileAgg
 
 from .evaluate import eval_expr, eval_filter, project  # noqa: F401
 
@@ -615,8 +616,8 @@ def reduce_column(col: Column, func: str):
     """Local partial reduction -> dict of partials (combined across ranks by
     the executor's _combine_reduce).  Reference role: the parallel agg
     combine in bodo/libs/_groupby_ftypes + distributed_api dist_reduce."""
-    if callable(func):
-        # custom python agg (LISTAGG / PERCENTILE_*): ship local values,
+    if callable(func) or isinstance(func, QuantileAgg):
+        # custom python agg (LISTAGG) or quantile: ship local values,
         # the combine applies the callable to the concatenation
         return {"vals_list": col.to_arrow().to_pylist()}
     if col.dtype.kind == TypeKind.DECIMAL128:

@@ -17,6 +17,7 @@ from ..core import types as bt
 from ..core.column import Column
 from ..core.table import Table
 from ..core.types import TypeKind
+from ..plan.nodes import QuantileAgg
 
 try:
     import bodo_amd_kernels as _K
@@ -623,12 +624,188 @@ _AGG_ONE = {
 def _agg_one(col: Optional[Column], row_gid: torch.Tensor, ngroups: int,
              func: str, uniq_rows: torch.Tensor, tbl: Table) -> Column:
     """One aggregate outside a fused batch, from its own launches."""
+    if isinstance(func, QuantileAgg):
+        return _quantile_by_group(col, row_gid, ngroups, func)
     if func not in _AGG_ONE:
         raise NotImplementedError(f"gpu agg {func}")
     return _AGG_ONE[func](col, row_gid, ngroups, func, uniq_rows)
 
 
+# Segmented radix select (csrc/segselect.hip): one order statistic and its
+# successor inside every group at once, for grouped median and quantile.
+# BODO_AMD_SEG_SELECT=0 sends the grouped median back to its two full sorts;
+# quantile aggregates have no other device route and always take the kernel.
+SEG_SELECT = os.environ.get("BODO_AMD_SEG_SELECT", "1") != "0"
+# the median takes the kernel from this many rows per group on average.
+# Measured (profiles/seg_select.md): it beat the sorts in every shape of 128
+# rows per group and more, one dominant group included, and lost for float64
+# at 16 rows per group (2^24 rows in 10^6 groups); nothing between was
+# measured.
+SEG_SELECT_MEDIAN_MIN_GROUP_ROWS = 128
+QUANTILE_INTERPOLATIONS = ("linear", "lower", "higher", "midpoint", "nearest")
+
+
+def seg_select(keys: torch.Tensor, seg_start: torch.Tensor,
+               rank: torch.Tensor, max_blocks: int = 2048):
+    """(lo, hi) per segment s = keys[seg_start[s]:seg_start[s + 1]]: the
+    keys of rank r = clamp(rank[s], 0, L - 1) and min(r + 1, L - 1) in the
+    sort's order (NaN last, -0.0 == 0.0), in the keys' dtype; zero for an
+    empty segment.  A NaN comes back as the canonical NaN, a zero as +0.0.
+    No host synchronisation."""
+    is_bool = keys.dtype == torch.bool
+    if is_bool:
+        keys = keys.view(torch.uint8)
+    if keys.numel() >= 2 ** 31:
+        raise ValueError("seg_select takes fewer than 2^31 rows")
+    lo, hi = kernels().seg_select(keys.contiguous(), seg_start.contiguous(),
+                                  rank.contiguous(), max_blocks)
+    return (lo.view(torch.bool), hi.view(torch.bool)) if is_bool else (lo, hi)
+
+
+# unsigned kinds wider than a byte: their storage is the signed dtype of the
+# same width or torch's unsigned one, and means the unsigned value either way
+_UNSIGNED_WIDE = {TypeKind.UINT16: (torch.int16, 16),
+                  TypeKind.UINT32: (torch.int32, 32),
+                  TypeKind.UINT64: (torch.int64, 64)}
+ORDER_STAT_KINDS = frozenset(bt._NUMERIC_KINDS) | {
+    TypeKind.BOOL, TypeKind.DATE32, TypeKind.TIMESTAMP_NS}
+
+
+def order_keys(col: Column):
+    """(keys, to_f64): the column's values in a dtype whose order under
+    seg_select is the values' order, and the function that turns selected
+    keys into the float64 values they stand for.  Wide unsigned columns are
+    viewed as signed with the top bit flipped, which keeps their order."""
+    if col.dtype.kind not in ORDER_STAT_KINDS:
+        raise TypeError(f"order statistics of a {col.dtype} column")
+    wide = _UNSIGNED_WIDE.get(col.dtype.kind)
+    if wide is None:
+        return col.data, lambda x: x.to(torch.float64)
+    signed, bits = wide
+    flip = -(1 << (bits - 1))
+
+    def to_f64(x):
+        raw = (x ^ flip).to(torch.int64)
+        if bits == 64:
+            # the upper half: halve with a sticky low bit, so that the one
+            # rounding is the rounding of the unsigned value
+            half = ((raw >> 1) & 0x7FFFFFFFFFFFFFFF) | (raw & 1)
+            return torch.where(raw < 0, half.to(torch.float64) * 2,
+                               raw.to(torch.float64))
+        return (raw & ((1 << bits) - 1)).to(torch.float64)
+
+    return col.data.view(signed) ^ flip, to_f64
+
+
+def group_segments(col: Column, row_gid: torch.Tensor, ngroups: int):
+    """(vals, seg_start, cnt, to_f64): the column's order_keys laid out group
+    by group, group g at vals[seg_start[g]:seg_start[g + 1]], the count per
+    group of the values that are neither null nor NaN, and order_keys'
+    conversion.  Null and NaN rows go to a trash segment behind the last
+    group, so nothing is compacted and the host reads nothing back."""
+    data, to_f64 = order_keys(col)
+    n = int(data.numel())
+    if n >= 2 ** 31:
+        raise ValueError("group_segments takes fewer than 2^31 rows")
+    gid = row_gid.to(torch.int64)
+    valid = ~torch.isnan(data) if col.dtype.is_float else None
+    if col.mask is not None:
+        valid = col.mask if valid is None else valid & col.mask
+    if valid is not None:
+        gid = torch.where(valid, gid, torch.full_like(gid, ngroups))
+    gid32 = gid.to(torch.int32)
+    if radix_route("partition", gid32):
+        order = radix_argsort(gid32, 0, max(1, ngroups.bit_length()))
+    else:
+        order = torch.argsort(gid, stable=True)
+    # segment bounds from the ordered ids: a count by atomics would put every
+    # row of a dominant group on one address
+    seg_start = torch.searchsorted(
+        gid[order], torch.arange(ngroups + 1, device=data.device))
+    return data[order], seg_start, seg_start[1:] - seg_start[:-1], to_f64
+
+
+def group_order_stats(col: Column, row_gid: torch.Tensor, ngroups: int,
+                      rank_of_count):
+    """(lo, hi, cnt) per group: cnt as in group_segments, lo the value of
+    rank r = rank_of_count(cnt) among the group's counted values and hi the
+    one of rank min(r + 1, cnt - 1), both as float64."""
+    vals, seg_start, cnt, to_f64 = group_segments(col, row_gid, ngroups)
+    lo, hi = seg_select(vals, seg_start, rank_of_count(cnt))
+    return to_f64(lo), to_f64(hi), cnt
+
+
+def _check_quantile(q: float, interpolation: str):
+    if not 0 <= q <= 1:
+        raise ValueError(f"quantile {q!r} is outside [0, 1]")
+    if interpolation not in QUANTILE_INTERPOLATIONS:
+        raise ValueError(f"interpolation {interpolation!r} is not one of "
+                         f"{QUANTILE_INTERPOLATIONS}")
+
+
+def quantile_ranks(cnt: torch.Tensor, q: float,
+                   interpolation: str = "linear") -> torch.Tensor:
+    """floor((cnt - 1) * q) as int64: the rank of the lower of the two order
+    statistics every interpolation reads."""
+    _check_quantile(q, interpolation)
+    h = (cnt - 1).clamp(min=0).to(torch.float64) * q
+    return h.floor().to(torch.int64)
+
+
+def quantile_finish(lo: torch.Tensor, hi: torch.Tensor, cnt: torch.Tensor,
+                    q: float, interpolation: str = "linear") -> torch.Tensor:
+    """The quantile, float64, from the order statistics of rank
+    quantile_ranks(cnt, q) and the one after it; NaN where cnt == 0.
+    `nearest` rounds half to even and `linear` is numpy's lerp."""
+    _check_quantile(q, interpolation)
+    a, b = lo.to(torch.float64), hi.to(torch.float64)
+    h = (cnt - 1).clamp(min=0).to(torch.float64) * q
+    fl = h.floor()
+    t = h - fl
+    if interpolation == "lower":
+        out = a
+    elif interpolation == "higher":
+        out = torch.where(t > 0, b, a)
+    elif interpolation == "nearest":
+        out = torch.where(h.round() > fl, b, a)
+    else:
+        if interpolation == "midpoint":
+            t = torch.where(t > 0, torch.full_like(t, 0.5), t)
+        d = b - a
+        out = torch.where(t >= 0.5, b - d * (1 - t), a + d * t)
+        out = torch.where(t == 0, a, out)
+    return torch.where(cnt == 0, torch.full_like(out, float("nan")), out)
+
+
+def _quantile_by_group(col: Column, row_gid: torch.Tensor, ngroups: int,
+                       func) -> Column:
+    lo, hi, cnt = group_order_stats(
+        col, row_gid, ngroups,
+        lambda c: quantile_ranks(c, func.q, func.interpolation))
+    return Column(bt.float64,
+                  quantile_finish(lo, hi, cnt, func.q, func.interpolation))
+
+
 def _median_by_group(col: Column, row_gid: torch.Tensor, ngroups: int) -> Column:
+    # wide unsigned columns stay with the sorts, which read their storage
+    # as it is
+    if not SEG_SELECT \
+            or col.data.numel() < SEG_SELECT_MEDIAN_MIN_GROUP_ROWS * ngroups \
+            or col.dtype.kind not in ORDER_STAT_KINDS \
+            or col.dtype.kind in _UNSIGNED_WIDE or not col.data.is_cuda \
+            or col.data.numel() >= 2 ** 31:
+        return _median_by_group_sort(col, row_gid, ngroups)
+    # converting to float64 is monotone: selecting first and converting the
+    # two middle values gives the numbers the sort of converted values gave
+    lo, hi, cnt = group_order_stats(col, row_gid, ngroups,
+                                    lambda c: (c - 1) // 2)
+    med = (lo + torch.where(cnt % 2 == 1, lo, hi)) / 2
+    return Column(bt.float64,
+                  torch.where(cnt == 0, torch.full_like(med, float("nan")), med))
+
+
+def _median_by_group_sort(col: Column, row_gid: torch.Tensor,
+                          ngroups: int) -> Column:
     # sort (gid, value) pairs; segmented median (device, torch-composable)
     vals = col.data.to(torch.float64)
     valid = ~torch.isnan(vals) if col.dtype.is_float else torch.ones_like(vals, dtype=torch.bool)

@@ -18,6 +18,7 @@ from ..core import types as bt
 from ..core.column import Column
 from ..core.table import Table
 from ..core.types import TypeKind
+from ..plan.nodes import QuantileAgg
 
 # physical agg funcs every backend implements
 PHYSICAL_AGGS = {
@@ -84,7 +85,8 @@ def groupby_local(tbl: Table, keys: Sequence[str],
             for o, i, f in aggs]
     tbl, aggs, dec_fix = _normalize_decimal_aggs(tbl, aggs)
     if tbl.device.type == "cuda":
-        if any(callable(a[2]) or a[2] in HOST_ONLY_AGGS for a in aggs):
+        if any(callable(a[2]) or a[2] in HOST_ONLY_AGGS
+               or _quantile_on_host(tbl, a) for a in aggs):
             # custom python agg: host pandas per co-located shard (the
             # @jit-to-HIP lowering is the native path for these)
             out = _groupby_pandas(tbl, keys, aggs, dropna)
@@ -106,6 +108,13 @@ def groupby_local(tbl: Table, keys: Sequence[str],
                 bt.float64, c.data / float(10 ** dec_dtype.scale), c.mask,
                 length=len(c)))
     return out
+
+
+def _quantile_on_host(tbl: Table, agg) -> bool:
+    """A quantile of a duration column keeps its pandas result type
+    (Timedelta), which the float64 device path does not produce."""
+    return (isinstance(agg[2], QuantileAgg) and tbl.has_column(agg[1])
+            and tbl.column(agg[1]).dtype.kind == TypeKind.DURATION_NS)
 
 
 def _groupby_pandas(tbl: Table, keys, aggs, dropna) -> Table:
@@ -135,6 +144,9 @@ def _groupby_pandas(tbl: Table, keys, aggs, dropna) -> Table:
             named[out_name] = pd.NamedAgg(
                 column=in_name,
                 aggfunc=lambda s: list(s.dropna()))
+        elif isinstance(func, QuantileAgg):
+            named[out_name] = pd.NamedAgg(column=in_name,
+                                          aggfunc=func.of_series)
         elif func == "size":
             named[out_name] = pd.NamedAgg(column=df.columns[0] if not in_name or in_name not in df.columns else in_name, aggfunc="size")
         else:

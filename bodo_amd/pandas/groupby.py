@@ -101,6 +101,9 @@ class DataFrameGroupBy:
     def median(self, numeric_only=False):
         return self._simple("median")
 
+    def quantile(self, q=0.5, interpolation="linear"):
+        return self._simple(_quantile_agg(q, interpolation))
+
     def first(self):
         return self._simple("first")
 
@@ -312,6 +315,9 @@ class SeriesGroupBy:
     def nunique(self):
         return self._agg1("nunique")
 
+    def quantile(self, q=0.5, interpolation="linear"):
+        return self._agg1(_quantile_agg(q, interpolation))
+
     def agg(self, func):
         if isinstance(func, str):
             return self._agg1(func)
@@ -459,6 +465,20 @@ class _IndexedAggResult:
 
     def __repr__(self):
         return repr(self.to_pandas().head(10))
+
+
+def _quantile_agg(q, interpolation) -> pn.QuantileAgg:
+    """The plan aggregate of a scalar quantile; a list of q has no native
+    path."""
+    import numbers
+
+    from ..ops.gpu import QUANTILE_INTERPOLATIONS
+
+    if not isinstance(q, numbers.Real):
+        raise NotImplementedError("groupby.quantile with a list of q")
+    if not 0 <= q <= 1 or interpolation not in QUANTILE_INTERPOLATIONS:
+        raise ValueError(f"quantile({q!r}, interpolation={interpolation!r})")
+    return pn.QuantileAgg(float(q), interpolation)
 
 
 def _norm_func(f):

@@ -308,19 +308,63 @@ class BodoSeries:
     product = prod
 
     def quantile(self, q=0.5, interpolation="linear"):
-        """Exact quantile: gathers the projected column (distributed shards
-        allgather) and interpolates with numpy.  For terabyte-scale inputs
+        """Exact quantile.  A numeric column held by one process on a GPU
+        stays there: one single-segment seg_select per q and one read-back.
+        Every other series gathers the projected column (distributed shards
+        allgather) and interpolates with numpy; for terabyte-scale inputs
         prefer .sample(...)-based estimates; groupby('...').median() stays
         fully distributed."""
-        ser = self.dropna().to_pandas()
+        from ..parallel import spawn
+
+        many = hasattr(q, "__len__")
+        qs = list(q) if many else [q]
+        ctx = ex.ExecutionContext()
+        if not spawn.active() and ctx.world == 1 and ctx.device.type == "cuda":
+            from ..engine import api
+
+            tbl = api.materialize(self._as_projection_plan())[1]
+            col = tbl.column("v")
+            if col.dtype.is_float or col.dtype.is_integer:
+                vals = self._quantile_gpu(col, qs, interpolation)
+                if many:
+                    return pd.Series(vals, index=qs, name=self.name)
+                return vals[0]
+            ser = tbl.to_pandas()["v"].dropna()  # not run a second time
+        else:
+            ser = self.dropna().to_pandas()
         from decimal import Decimal as _D
 
         if len(ser) and isinstance(ser.iloc[0], _D):
             ser = ser.astype(float)
-        if hasattr(q, "__len__"):
+        if many:
             return pd.Series([ser.quantile(x, interpolation=interpolation)
-                              for x in q], index=list(q), name=self.name)
+                              for x in q], index=qs, name=self.name)
         return ser.quantile(q, interpolation=interpolation)
+
+    @staticmethod
+    def _quantile_gpu(col, qs, interpolation):
+        import torch
+
+        from ..ops import gpu
+
+        if col.mask is None:
+            # NaN orders last, so the whole column is the segment and the
+            # ranks stop short of the NaNs
+            vals, to_f64 = gpu.order_keys(col)
+            n = torch.tensor([len(col)], device=vals.device)
+            seg_start = torch.cat([torch.zeros_like(n), n])
+            cnt = n - torch.isnan(vals).sum() if col.dtype.is_float else n
+        else:
+            gid = torch.zeros(len(col), dtype=torch.int32,
+                              device=col.data.device)
+            vals, seg_start, cnt, to_f64 = gpu.group_segments(col, gid, 1)
+        outs = []
+        for q in qs:
+            lo, hi = gpu.seg_select(
+                vals, seg_start, gpu.quantile_ranks(cnt, q, interpolation))
+            outs.append(gpu.quantile_finish(to_f64(lo), to_f64(hi), cnt, q,
+                                            interpolation))
+        return torch.cat(outs).cpu().tolist()
 
     def median(self):
         return self.quantile(0.5)

@@ -94,11 +94,26 @@ class Filter(PlanNode):
 
 
 @dataclass(frozen=True)
+class QuantileAgg:
+    """The `func` of an (out_name, in_name, func) aggregate that takes
+    parameters: the q-quantile under one of pandas' interpolations.  Not
+    callable, so no backend mistakes it for a python aggregate; needs whole
+    groups in one place, like median."""
+
+    q: float
+    interpolation: str = "linear"
+
+    def of_series(self, ser):
+        return ser.quantile(self.q, interpolation=self.interpolation)
+
+
+@dataclass(frozen=True)
 class Aggregate(PlanNode):
     child: PlanNode
     keys: Tuple[str, ...] = ()
     # aggs: (out_name, in_name, func); func in
-    # sum/count/mean/min/max/size/nunique/first/last/var/std/median/prod
+    # sum/count/mean/min/max/size/nunique/first/last/var/std/median/prod,
+    # a QuantileAgg or a python callable
     aggs: Tuple[Tuple[str, str, str], ...] = ()
     as_index: bool = False
     dropna: bool = True

@@ -1181,8 +1181,7 @@ class Planner:
                                 in_name = self._uniq("__ain")
                                 pre_exprs[in_name] = self.expr(oe, scope)
                                 pre_names.append(in_name)
-                        func = (lambda s_, _q=qv, _i=interp:
-                                s_.quantile(_q, interpolation=_i))
+                        func = pn.QuantileAgg(qv, interp)
                     elif e.name in ("listagg", "string_agg"):
                         sep = e.args[1].value if len(e.args) > 1 else ""
                         wo = getattr(e, "within_order", None)

@@ -1522,6 +1522,13 @@ c10::optional<torch::Tensor> radix_select(torch::Tensor keys, int64_t k,
                                           int64_t max_blocks);
 int64_t select_capacity(int64_t n);
 
+// segselect.hip: one order statistic and its successor in every segment
+std::vector<torch::Tensor> seg_select(torch::Tensor keys,
+                                      torch::Tensor seg_start,
+                                      torch::Tensor rank, int64_t max_blocks);
+int64_t seg_wave_keys();
+int64_t seg_block_keys();
+
 // window.hip: segmented scan over head-flagged rows, rolling min/max finish
 std::vector<torch::Tensor> seg_scan(torch::Tensor values,
                                     c10::optional<torch::Tensor> invalid,
@@ -1608,6 +1615,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("max_out") = -1, py::arg("max_blocks") = 2048);
   m.def("select_capacity", &select_capacity,
         "keys the survivor buffer of radix_select holds for n rows");
+  m.def("seg_select", &seg_select,
+        "(lo, hi): the keys of rank clamp(rank[s], 0, L - 1) and the rank "
+        "after it (clamped) of keys[seg_start[s]:seg_start[s + 1]], in the "
+        "sort's order and the keys' dtype",
+        py::arg("keys"), py::arg("seg_start"), py::arg("rank"),
+        py::arg("max_blocks") = 2048);
+  m.attr("SEG_WAVE_KEYS") = seg_wave_keys();
+  m.attr("SEG_BLOCK_KEYS") = seg_block_keys();
   m.def("seg_scan", &seg_scan,
         "segmented inclusive scan (op 0 SUM_F64, 1 SUM_I64, 2 MIN_F64, "
         "3 MAX_F64) of values over head-flagged segments -> [acc] or "

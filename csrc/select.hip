@@ -75,53 +75,6 @@ DEV_INLINE uint64_t select_key(uint64_t norm, int begin_bit, uint64_t wmask) {
   return (norm >> begin_bit) & wmask;
 }
 
-// The tile's keys for this thread, in no particular order: k[j] is valid
-// where bit j of the returned mask is set.  Whole tiles of an aligned column
-// go through 16-byte loads (8-byte for one-byte dtypes: a thread owns 8
-// keys per tile), the ragged last tile through guarded scalar loads.
-template <int WB>
-DEV_INLINE uint32_t select_load_tile(const void* __restrict__ src, int kind,
-                                     int64_t base, int64_t end, bool aligned,
-                                     int t, uint64_t k[RS_KPT]) {
-  constexpr int V = WB == 8 ? 2 : WB == 4 ? 4 : 8;  // keys per vector load
-  if (aligned && base + RS_TILE <= end) {
-#pragma unroll
-    for (int v = 0; v < RS_KPT / V; ++v) {
-      const char* p = (const char*)src +
-                      (base + ((int64_t)v * RS_THREADS + t) * V) * WB;
-      if constexpr (V * WB == 16) {
-        uint4 raw = *(const uint4*)p;
-#pragma unroll
-        for (int j = 0; j < V; ++j) k[v * V + j] = radix_norm(&raw, kind, j);
-      } else {
-        uint2 raw = *(const uint2*)p;
-#pragma unroll
-        for (int j = 0; j < V; ++j) k[v * V + j] = radix_norm(&raw, kind, j);
-      }
-    }
-    return (1u << RS_KPT) - 1u;
-  }
-  uint32_t ok = 0;
-#pragma unroll
-  for (int j = 0; j < RS_KPT; ++j) {
-    int64_t i = base + j * RS_THREADS + t;
-    bool in = i < end;
-    k[j] = in ? radix_norm(src, kind, i) : 0;
-    ok |= (uint32_t)in << j;
-  }
-  return ok;
-}
-
-// the kinds a kernel built for WB-byte keys can meet, so that radix_norm's
-// switch folds to them
-template <int WB>
-DEV_INLINE int select_kind(int kind) {
-  if (WB == 1) return kind == RK_U8 ? RK_U8 : RK_I8;
-  if (WB == 2) return RK_I16;
-  if (WB == 4) return kind == RK_F32 ? RK_F32 : RK_I32;
-  return kind == RK_F64 ? RK_F64 : RK_I64;
-}
-
 // ---------------------------------------------------------------- histogram
 
 // One tile's keys into the wave-private histogram; with `fill`, the matching
@@ -210,25 +163,6 @@ __global__ __launch_bounds__(RS_THREADS) void select_hist_kernel(
   uint32_t s = 0;
   for (int w = 0; w < RS_WAVES; ++w) s += hist[w][t];
   if (s) atomicAdd(&st->hist[t], s);
-}
-
-// exclusive scan of one value per thread over the block's 256 threads;
-// *all gets the block total
-DEV_INLINE uint32_t select_block_excl_scan(uint32_t v, uint32_t* wsum, int t,
-                                           uint32_t* all) {
-  const int lane = t % WAVE, wave = t / WAVE;
-  uint32_t inc = wave_incl_scan(v, lane);
-  if (lane == WAVE - 1) wsum[wave] = inc;
-  __syncthreads();
-  uint32_t before = 0, total = 0;
-  for (int w = 0; w < RS_WAVES; ++w) {
-    uint32_t x = wsum[w];
-    if (w < wave) before += x;
-    total += x;
-  }
-  __syncthreads();
-  *all = total;
-  return before + inc - v;
 }
 
 // One block after every histogram: pick the bin that holds the rank, extend
