@@ -35,6 +35,23 @@ def kernels():
     return _K
 
 
+def _check_rows(x: torch.Tensor, who: str) -> None:
+    if x.numel() >= 2 ** 31:
+        raise ValueError(f"{who} takes fewer than 2^31 rows")
+
+
+def _ext_flags(x: torch.Tensor) -> torch.Tensor:
+    """`x` as the extension takes it: bool viewed as uint8, contiguous."""
+    return (x.view(torch.uint8) if x.dtype == torch.bool else x).contiguous()
+
+
+def _ext_keys(x: torch.Tensor, who: str) -> torch.Tensor:
+    """A key or value tensor for the extension: fewer than 2^31 rows, bool
+    viewed as uint8, contiguous."""
+    _check_rows(x, who)
+    return _ext_flags(x)
+
+
 def _fnv_bytes(b: bytes) -> int:
     h = 0xcbf29ce484222325
     for ch in b:
@@ -653,12 +670,9 @@ def seg_select(keys: torch.Tensor, seg_start: torch.Tensor,
     empty segment.  A NaN comes back as the canonical NaN, a zero as +0.0.
     No host synchronisation."""
     is_bool = keys.dtype == torch.bool
-    if is_bool:
-        keys = keys.view(torch.uint8)
-    if keys.numel() >= 2 ** 31:
-        raise ValueError("seg_select takes fewer than 2^31 rows")
-    lo, hi = kernels().seg_select(keys.contiguous(), seg_start.contiguous(),
-                                  rank.contiguous(), max_blocks)
+    lo, hi = kernels().seg_select(_ext_keys(keys, "seg_select"),
+                                  seg_start.contiguous(), rank.contiguous(),
+                                  max_blocks)
     return (lo.view(torch.bool), hi.view(torch.bool)) if is_bool else (lo, hi)
 
 
@@ -1132,13 +1146,11 @@ def radix_argsort(keys: torch.Tensor, begin_bit: int = 0,
     """p[argsort(K[p], stable=True)] as int64, where K is `keys` restricted
     to bits [begin_bit, end_bit) of its order-preserving unsigned form
     (end_bit None: the dtype's width) and p is `perm` or the identity."""
-    if keys.dtype == torch.bool:
-        keys = keys.view(torch.uint8)
-    n = keys.numel() if perm is None else perm.numel()
-    if max(n, keys.numel()) >= 2 ** 31:
-        raise ValueError("radix_argsort takes fewer than 2^31 rows")
+    if perm is not None:
+        _check_rows(perm, "radix_argsort")
     return kernels().radix_argsort(
-        keys.contiguous(), begin_bit, -1 if end_bit is None else end_bit,
+        _ext_keys(keys, "radix_argsort"), begin_bit,
+        -1 if end_bit is None else end_bit,
         None if perm is None else perm.contiguous())
 
 
@@ -1178,17 +1190,14 @@ def radix_select(keys: torch.Tensor, k: int, begin_bit: int = 0,
     if ties not in ("first", "all"):
         raise ValueError(f"radix_select: ties must be 'first' or 'all', "
                          f"not {ties!r}")
-    if keys.dtype == torch.bool:
-        keys = keys.view(torch.uint8)
+    _check_rows(keys, "radix_select")
     n = keys.numel()
-    if n >= 2 ** 31:
-        raise ValueError("radix_select takes fewer than 2^31 rows")
     if k <= 0 or n == 0:
         return torch.empty(0, dtype=torch.int64, device=keys.device)
     if k >= n:
         return torch.arange(n, dtype=torch.int64, device=keys.device)
     return kernels().radix_select(
-        keys.contiguous(), k, begin_bit, -1 if end_bit is None else end_bit,
+        _ext_keys(keys, "radix_select"), k, begin_bit, -1 if end_bit is None else end_bit,
         ties == "all", -1 if max_out is None else max_out, max_blocks)
 
 
@@ -1200,8 +1209,7 @@ SEG_SCAN = os.environ.get("BODO_AMD_SEG_SCAN", "1") != "0"
 # width - 1 passes were faster when measured (profiles/seg_scan.md)
 SEG_SCAN_ROLLING_MINMAX_MIN_WIDTH = 4
 SEG_SCAN_OPS = {"sum_f64": 0, "sum_i64": 1, "min_f64": 2, "max_f64": 3}
-SEG_SCAN_DTYPES = (torch.int8, torch.int16, torch.int32, torch.int64,
-                   torch.uint8, torch.bool, torch.float32, torch.float64)
+SEG_SCAN_DTYPES = _RADIX_DTYPES  # engine/window.py reads this name
 
 
 def segmented_scan(values: torch.Tensor, heads: torch.Tensor, op: str,
@@ -1211,13 +1219,9 @@ def segmented_scan(values: torch.Tensor, heads: torch.Tensor, op: str,
     restarts at every row whose `heads` flag is set; rows flagged `invalid`
     contribute nothing.  reverse scans each segment from its last row.
     Returns acc, or (acc, running count of valid rows) with want_count."""
-    def u8(x):
-        return (x.view(torch.uint8) if x.dtype == torch.bool else x).contiguous()
-
-    if values.numel() >= 2 ** 31:
-        raise ValueError("segmented_scan takes fewer than 2^31 rows")
     out = kernels().seg_scan(
-        u8(values), None if invalid is None else u8(invalid), u8(heads),
+        _ext_keys(values, "segmented_scan"),
+        None if invalid is None else _ext_flags(invalid), _ext_flags(heads),
         SEG_SCAN_OPS[op], reverse, want_count)
     return tuple(out) if want_count else out[0]
 

@@ -9,10 +9,9 @@
 // GEMM-peak bound.
 
 #include <torch/extension.h>
-#include <c10/hip/HIPStream.h>
-#include <hip/hip_runtime.h>
 
 #include "common.h"
+#include "hip_host.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -91,11 +90,9 @@ torch::Tensor gemm_f32(torch::Tensor A, torch::Tensor B) {
   auto C = torch::empty({M, N},
                         torch::dtype(torch::kFloat32).device(A.device()));
   dim3 grid((N + BN - 1) / BN, (M + BM - 1) / BM);
-  hipLaunchKernelGGL(gemm_f32_kernel, grid, dim3(256), 0,
-                     c10::hip::getCurrentHIPStream().stream(),
+  hipLaunchKernelGGL(gemm_f32_kernel, grid, dim3(256), 0, current_stream(),
                      (const float*)Ac.data_ptr(), (const float*)Bc.data_ptr(),
                      (float*)C.data_ptr(), M, N, K, 0.0f);
-  hipError_t e = hipGetLastError();
-  TORCH_CHECK(e == hipSuccess, "HIP error: ", hipGetErrorString(e));
+  CHECK_HIP(hipGetLastError());
   return C;
 }

@@ -15,24 +15,14 @@
 
 #include <torch/extension.h>
 #include <ATen/ATen.h>
-#include <c10/hip/HIPStream.h>
 
 #include <cstring>
 #include <memory>
 #include <vector>
 
 #include "common.h"
+#include "hip_host.h"
 #include "parquet.h"
-
-#define CHECK_HIP(x)                                                    \
-  do {                                                                  \
-    hipError_t e = (x);                                                 \
-    TORCH_CHECK(e == hipSuccess, "HIP error: ", hipGetErrorString(e));  \
-  } while (0)
-
-static hipStream_t cur_stream() {
-  return c10::hip::getCurrentHIPStream().stream();
-}
 
 // ---------------------------------------------------------------------
 // ColumnDesc marshalling
@@ -113,7 +103,7 @@ torch::Tensor hash_columns(
   auto out = torch::empty({n}, torch::dtype(torch::kInt64).device(dev));
   int block = 256;
   hipLaunchKernelGGL(hash_columns_kernel, dim3(grid_for(n, block)),
-                     dim3(block), 0, cur_stream(), ds.ptr(),
+                     dim3(block), 0, current_stream(), ds.ptr(),
                      (int)datas.size(), (uint64_t)seed,
                      (uint64_t*)out.data_ptr(), n);
   CHECK_HIP(hipGetLastError());
@@ -216,17 +206,17 @@ torch::Tensor dt_field(torch::Tensor data, int64_t is_date32, int64_t field,
   if (out_kind == 0) {  // int16
     out = torch::empty({n}, torch::dtype(torch::kInt16).device(dev));
     hipLaunchKernelGGL(dt_field_kernel<int16_t>, grid, dim3(block), 0,
-                       cur_stream(), ts, (int)is_date32, ts32, (int)field,
+                       current_stream(), ts, (int)is_date32, ts32, (int)field,
                        (int16_t*)out.data_ptr(), n);
   } else if (out_kind == 1) {  // int32
     out = torch::empty({n}, torch::dtype(torch::kInt32).device(dev));
     hipLaunchKernelGGL(dt_field_kernel<int32_t>, grid, dim3(block), 0,
-                       cur_stream(), ts, (int)is_date32, ts32, (int)field,
+                       current_stream(), ts, (int)is_date32, ts32, (int)field,
                        (int32_t*)out.data_ptr(), n);
   } else {  // int64
     out = torch::empty({n}, torch::dtype(torch::kInt64).device(dev));
     hipLaunchKernelGGL(dt_field_kernel<int64_t>, grid, dim3(block), 0,
-                       cur_stream(), ts, (int)is_date32, ts32, (int)field,
+                       current_stream(), ts, (int)is_date32, ts32, (int)field,
                        (int64_t*)out.data_ptr(), n);
   }
   CHECK_HIP(hipGetLastError());
@@ -272,7 +262,7 @@ std::vector<torch::Tensor> gather_string(torch::Tensor bytes,
     int waves_per_block = block / WAVE;
     int grid = (int)std::min<int64_t>((n + waves_per_block - 1) / waves_per_block, 2048);
     hipLaunchKernelGGL(string_gather_kernel, dim3(grid), dim3(block), 0,
-                       cur_stream(), (const uint8_t*)bytes.data_ptr(),
+                       current_stream(), (const uint8_t*)bytes.data_ptr(),
                        (const int64_t*)offsets.data_ptr(),
                        (const int64_t*)idx.data_ptr(),
                        (const int64_t*)new_off.data_ptr(),
@@ -480,7 +470,7 @@ static CompactedSlots compact_slots(Slots table, int64_t cap,
   auto block_counts = torch::zeros({nblocks},
                                    torch::dtype(torch::kInt64).device(dev));
   hipLaunchKernelGGL(gb_count_kernel<Slots>, dim3(nblocks), dim3(block), 0,
-                     cur_stream(), table, chunk, cap,
+                     current_stream(), table, chunk, cap,
                      (int64_t*)block_counts.data_ptr());
   CHECK_HIP(hipGetLastError());
   auto block_base = torch::zeros({nblocks}, torch::dtype(torch::kInt64).device(dev));
@@ -500,7 +490,7 @@ static CompactedSlots compact_slots(Slots table, int64_t cap,
   out.uniq_rows = torch::empty({std::max<int64_t>(out.ngroups, 1)},
                                torch::dtype(torch::kInt64).device(dev));
   hipLaunchKernelGGL(gb_assign_gid_kernel<Slots>, dim3(nblocks), dim3(block),
-                     0, cur_stream(), table, chunk, cap,
+                     0, current_stream(), table, chunk, cap,
                      (const int64_t*)block_base.data_ptr(),
                      want_slot_gid ? (int32_t*)out.slot_gid.data_ptr() : nullptr,
                      (int64_t*)out.uniq_rows.data_ptr());
@@ -558,7 +548,7 @@ static std::vector<torch::Tensor> build_groups(
   auto& uniq_rows = groups.uniq_rows;
   auto row_gid = torch::empty({n}, torch::dtype(torch::kInt32).device(dev));
   hipLaunchKernelGGL(gb_rowgid_kernel, dim3(grid_for(n, block)), dim3(block),
-                     0, cur_stream(), (const uint32_t*)row_slot.data_ptr(),
+                     0, current_stream(), (const uint32_t*)row_slot.data_ptr(),
                      (const int32_t*)slot_gid.data_ptr(),
                      (int32_t*)row_gid.data_ptr(), n);
   CHECK_HIP(hipGetLastError());
@@ -579,7 +569,7 @@ std::vector<torch::Tensor> groupby_build_packed(torch::Tensor keys,
       },
       [&](int64_t cap, int64_t start, int64_t cnt, uint32_t* row_slot) {
         hipLaunchKernelGGL(gb_insert_packed_kernel, dim3(grid_for(cnt, 256)),
-                           dim3(256), 0, cur_stream(),
+                           dim3(256), 0, current_stream(),
                            (const int64_t*)keys.data_ptr() + start,
                            (unsigned long long*)slot_keys.data_ptr(),
                            (uint32_t*)slot_rows.data_ptr(), (uint64_t)(cap - 1),
@@ -614,7 +604,7 @@ std::vector<torch::Tensor> groupby_build(
       },
       [&](int64_t cap, int64_t start, int64_t cnt, uint32_t* row_slot) {
         hipLaunchKernelGGL(gb_insert_kernel, dim3(grid_for(cnt, 256)),
-                           dim3(256), 0, cur_stream(), ds.ptr(),
+                           dim3(256), 0, current_stream(), ds.ptr(),
                            (int)datas.size(),
                            (const uint64_t*)hashes.data_ptr() + start,
                            (uint32_t*)slots.data_ptr(), (uint64_t)(cap - 1),
@@ -890,12 +880,12 @@ std::vector<torch::Tensor> agg_update_fused(
   size_t lds_bytes = (size_t)n_aggs * (size_t)ngroups * 16;
   if (lds_bytes <= 48 * 1024) {
     hipLaunchKernelGGL(agg_update_fused_lds_kernel, dim3(grid_for(n, block)),
-                       dim3(block), lds_bytes, cur_stream(), fas[0], fas[1],
+                       dim3(block), lds_bytes, current_stream(), fas[0], fas[1],
                        fas[2], fas[3], n_aggs, (int)ngroups,
                        (const int32_t*)row_gid.data_ptr(), n);
   } else {
     hipLaunchKernelGGL(agg_update_fused_kernel, dim3(grid_for(n, block)),
-                       dim3(block), 0, cur_stream(), fas[0], fas[1], fas[2],
+                       dim3(block), 0, current_stream(), fas[0], fas[1], fas[2],
                        fas[3], n_aggs, (const int32_t*)row_gid.data_ptr(), n);
   }
   CHECK_HIP(hipGetLastError());
@@ -916,13 +906,13 @@ std::vector<torch::Tensor> agg_update(
   bool lds_ok = ngroups <= LDS_AGG_MAX_GROUPS && op != AGG_PROD_F64;
   if (lds_ok) {
     hipLaunchKernelGGL(agg_update_lds_kernel, dim3(grid_for(n, block)),
-                       dim3(block), 0, cur_stream(), col,
+                       dim3(block), 0, current_stream(), col,
                        (const int32_t*)row_gid.data_ptr(), (int)op,
                        (int)ngroups, acc.data_ptr(), cnt_ptr, n,
                        init_f, init_i);
   } else {
     hipLaunchKernelGGL(agg_update_kernel, dim3(grid_for(n, block)), dim3(block),
-                       0, cur_stream(), col,
+                       0, current_stream(), col,
                        (const int32_t*)row_gid.data_ptr(), (int)op,
                        acc.data_ptr(), cnt_ptr, n);
   }
@@ -1143,12 +1133,12 @@ std::vector<torch::Tensor> groupby_dense_fused(
   auto err = torch::zeros({1}, i64);
   int block = 256;
   hipLaunchKernelGGL(dense_init_kernel, dim3(grid_for(nslots * words, block)),
-                     dim3(block), 0, cur_stream(),
+                     dim3(block), 0, current_stream(),
                      (uint64_t*)table.data_ptr(), words, init_bits[0],
                      init_bits[1], init_bits[2], init_bits[3], nslots);
   CHECK_HIP(hipGetLastError());
   hipLaunchKernelGGL(groupby_dense_fused_kernel, dim3(grid_for(n, block)),
-                     dim3(block), 0, cur_stream(), keys, aggs,
+                     dim3(block), 0, current_stream(), keys, aggs,
                      (uint64_t*)table.data_ptr(), (int64_t*)err.data_ptr(), n);
   CHECK_HIP(hipGetLastError());
   DenseSlots view{(const uint64_t*)table.data_ptr(), words};
@@ -1159,7 +1149,7 @@ std::vector<torch::Tensor> groupby_dense_fused(
   auto cnt = torch::empty({1 + n_aggs, ngroups}, i64);
   if (ngroups) {
     hipLaunchKernelGGL(dense_gather_kernel, dim3(grid_for(ngroups, block)),
-                       dim3(block), 0, cur_stream(),
+                       dim3(block), 0, current_stream(),
                        (const uint64_t*)table.data_ptr(), aggs,
                        (const int64_t*)groups.uniq_rows.data_ptr(),
                        (uint64_t*)acc.data_ptr(), (int64_t*)cnt.data_ptr(),
@@ -1260,7 +1250,7 @@ std::vector<torch::Tensor> join_build(torch::Tensor hashes, int64_t n_build) {
   if (n_build) {
     int block = 256;
     hipLaunchKernelGGL(join_build_kernel, dim3(grid_for(n_build, block)),
-                       dim3(block), 0, cur_stream(),
+                       dim3(block), 0, current_stream(),
                        (const uint64_t*)hashes.data_ptr(),
                        (uint32_t*)heads.data_ptr(),
                        (uint32_t*)next.data_ptr(), (uint64_t)(cap - 1),
@@ -1294,7 +1284,7 @@ std::vector<torch::Tensor> join_probe(
   if (n_probe) {
     hipLaunchKernelGGL(join_probe_count_kernel,
                        dim3(grid_for(n_probe, block)), dim3(block), 0,
-                       cur_stream(), bds.ptr(), pds.ptr(), (int)bdatas.size(),
+                       current_stream(), bds.ptr(), pds.ptr(), (int)bdatas.size(),
                        (const uint64_t*)bh.data_ptr(),
                        (const uint64_t*)ph.data_ptr(),
                        (const uint32_t*)heads.data_ptr(),
@@ -1320,7 +1310,7 @@ std::vector<torch::Tensor> join_probe(
   if (n_probe && total) {
     hipLaunchKernelGGL(join_probe_fill_kernel,
                        dim3(grid_for(n_probe, block)), dim3(block), 0,
-                       cur_stream(), bds.ptr(), pds.ptr(), (int)bdatas.size(),
+                       current_stream(), bds.ptr(), pds.ptr(), (int)bdatas.size(),
                        (const uint64_t*)bh.data_ptr(),
                        (const uint64_t*)ph.data_ptr(),
                        (const uint32_t*)heads.data_ptr(),
@@ -1390,7 +1380,7 @@ std::vector<torch::Tensor> join_probe_dense(
   if (n_probe) {
     int block = 256;
     hipLaunchKernelGGL(join_probe_dense_kernel, dim3(grid_for(n_probe, block)),
-                       dim3(block), 0, cur_stream(), pdata.data_ptr(),
+                       dim3(block), 0, current_stream(), pdata.data_ptr(),
                        pmask.has_value() ? (const uint8_t*)pmask->data_ptr()
                                          : nullptr,
                        (int)pdtype, (const int32_t*)lut.data_ptr(),
@@ -1459,7 +1449,7 @@ torch::Tensor rle_expand(torch::Tensor runs_blob, int64_t n_runs,
     int grid = (int)std::min<int64_t>(
         (n_runs + waves_per_block - 1) / waves_per_block, 2048);
     hipLaunchKernelGGL(rle_expand_kernel, dim3(grid), dim3(block), 0,
-                       cur_stream(), (const RleRun*)runs_blob.data_ptr(),
+                       current_stream(), (const RleRun*)runs_blob.data_ptr(),
                        (int)n_runs, (const uint8_t*)packed.data_ptr(),
                        (int)bitwidth, (int32_t*)out.data_ptr());
     CHECK_HIP(hipGetLastError());

@@ -35,17 +35,8 @@
 #include <vector>
 
 #include "common.h"
+#include "hip_host.h"
 #include "parquet.h"
-
-#define CHECK_HIP_PQ(x)                                                 \
-  do {                                                                  \
-    hipError_t e = (x);                                                 \
-    TORCH_CHECK(e == hipSuccess, "HIP error: ", hipGetErrorString(e));  \
-  } while (0)
-
-static hipStream_t pq_stream() {
-  return c10::hip::getCurrentHIPStream().stream();
-}
 
 // Per data-page metadata, filled on host from page headers.
 struct PageMeta {
@@ -842,11 +833,11 @@ void pq_decompress(torch::Tensor src, torch::Tensor pages_blob,
                    int64_t n_pages, torch::Tensor scratch) {
   if (!n_pages) return;
   hipLaunchKernelGGL(pq_decompress_kernel, dim3(pq_grid_pages(n_pages)),
-                     dim3(WAVE), 0, pq_stream(),
+                     dim3(WAVE), 0, current_stream(),
                      (const uint8_t*)src.data_ptr(),
                      (const PageMeta*)pages_blob.data_ptr(), (int)n_pages,
                      (uint8_t*)scratch.data_ptr());
-  CHECK_HIP_PQ(hipGetLastError());
+  CHECK_HIP(hipGetLastError());
 }
 
 // The two group launchers: argument checks and launches on the stream they
@@ -860,7 +851,7 @@ static void pq_launch_decompress_multi(const void* pages, int64_t avail,
   hipLaunchKernelGGL(pq_decompress_multi_kernel,
                      dim3(pq_grid_pages(n_pages)), dim3(WAVE), 0, stream,
                      (const PagePtr*)pages, (int)n_pages);
-  CHECK_HIP_PQ(hipGetLastError());
+  CHECK_HIP(hipGetLastError());
 }
 
 // Two launches whatever the table holds: PLAIN pages one block each, codes
@@ -880,11 +871,11 @@ static void pq_launch_values_multi(const void* pages, int64_t avail,
   hipLaunchKernelGGL(pq_values_multi_kernel<false>, dim3(grid), dim3(256), 0,
                      stream, (const ValPage*)pages, (int)n_pages,
                      (int32_t*)err.data_ptr());
-  CHECK_HIP_PQ(hipGetLastError());
+  CHECK_HIP(hipGetLastError());
   hipLaunchKernelGGL(pq_values_multi_kernel<true>, dim3(grid), dim3(WAVE), 0,
                      stream, (const ValPage*)pages, (int)n_pages,
                      (int32_t*)err.data_ptr());
-  CHECK_HIP_PQ(hipGetLastError());
+  CHECK_HIP(hipGetLastError());
 }
 
 // pages_blob: device bytes of n_pages PagePtr entries (absolute device
@@ -894,7 +885,7 @@ void pq_decompress_multi(torch::Tensor pages_blob, int64_t n_pages) {
               "pq_decompress_multi: page table too small");
   pq_launch_decompress_multi(pages_blob.data_ptr(),
                              pages_blob.numel() * pages_blob.element_size(),
-                             n_pages, pq_stream());
+                             n_pages, current_stream());
 }
 
 // pages_blob: device bytes of n_pages ValPage entries; err: one int32 on
@@ -905,7 +896,7 @@ void pq_values_multi(torch::Tensor pages_blob, int64_t n_pages,
               "pq_values_multi: page table too small");
   pq_launch_values_multi(pages_blob.data_ptr(),
                          pages_blob.numel() * pages_blob.element_size(),
-                         n_pages, err, pages_blob.device(), pq_stream());
+                         n_pages, err, pages_blob.device(), current_stream());
 }
 
 // ---------------------------------------------------------------------
@@ -919,17 +910,17 @@ void pq_values_multi(torch::Tensor pages_blob, int64_t n_pages,
 // ---------------------------------------------------------------------
 
 PqDone::PqDone(int device) : device(device) {
-  CHECK_HIP_PQ(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  CHECK_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
 }
 
 PqDone::~PqDone() { (void)hipEventDestroy(ev); }
 
-void PqDone::synchronize() { CHECK_HIP_PQ(hipEventSynchronize(ev)); }
+void PqDone::synchronize() { CHECK_HIP(hipEventSynchronize(ev)); }
 
 bool PqDone::query() {
   hipError_t e = hipEventQuery(ev);
   if (e == hipErrorNotReady) return false;
-  CHECK_HIP_PQ(e);
+  CHECK_HIP(e);
   return true;
 }
 
@@ -950,7 +941,7 @@ PqDecodeStream& pq_decode_stream(c10::DeviceIndex device) {
   if ((size_t)device >= streams.size()) streams.resize(device + 1);
   if (!streams[device]) {
     hipEvent_t ready;
-    CHECK_HIP_PQ(hipEventCreateWithFlags(&ready, hipEventDisableTiming));
+    CHECK_HIP(hipEventCreateWithFlags(&ready, hipEventDisableTiming));
     streams[device].reset(new PqDecodeStream{
         c10::hip::getStreamFromPoolMasqueradingAsCUDA(
             /*isHighPriority=*/false, device).hip_stream(), ready});
@@ -988,9 +979,9 @@ std::shared_ptr<PqDone> pq_decode_group(torch::Tensor blob, int64_t dec_bytes,
   hipStream_t side = ds.stream.stream();
 
   // after the group's last chunk upload and the table upload
-  CHECK_HIP_PQ(hipEventRecord(
+  CHECK_HIP(hipEventRecord(
       ds.ready, c10::hip::getCurrentHIPStream(dev.index()).stream()));
-  CHECK_HIP_PQ(hipStreamWaitEvent(side, ds.ready, 0));
+  CHECK_HIP(hipStreamWaitEvent(side, ds.ready, 0));
 
   const uint8_t* base = (const uint8_t*)blob.data_ptr();
   pq_launch_decompress_multi(base, dec_bytes, n_dec, side);
@@ -1002,7 +993,7 @@ std::shared_ptr<PqDone> pq_decode_group(torch::Tensor blob, int64_t dec_bytes,
     c10::hip::HIPCachingAllocator::recordStream(t.storage().data_ptr(),
                                                 ds.stream);
   auto done = std::make_shared<PqDone>((int)dev.index());
-  CHECK_HIP_PQ(hipEventRecord(done->ev, side));
+  CHECK_HIP(hipEventRecord(done->ev, side));
   return done;
 }
 
@@ -1010,7 +1001,7 @@ std::shared_ptr<PqDone> pq_decode_group(torch::Tensor blob, int64_t dec_bytes,
 void pq_decode_join(std::shared_ptr<PqDone> done) {
   TORCH_CHECK(done != nullptr, "pq_decode_join: no event");
   c10::hip::HIPGuard guard((c10::DeviceIndex)done->device);
-  CHECK_HIP_PQ(hipStreamWaitEvent(
+  CHECK_HIP(hipStreamWaitEvent(
       c10::hip::getCurrentHIPStream((c10::DeviceIndex)done->device).stream(),
       done->ev, 0));
 }
@@ -1028,13 +1019,13 @@ std::vector<torch::Tensor> pq_def_levels(torch::Tensor scratch,
     int block = 256;
     hipLaunchKernelGGL(pq_def_levels_kernel,
                        dim3(pq_grid_waves(n_pages, block)), dim3(block), 0,
-                       pq_stream(), (const uint8_t*)scratch.data_ptr(),
+                       current_stream(), (const uint8_t*)scratch.data_ptr(),
                        (const PageMeta*)pages_blob.data_ptr(), (int)n_pages,
                        (int)bitwidth, (int)max_def,
                        (uint8_t*)mask.data_ptr(),
                        (int32_t*)n_valid.data_ptr(),
                        (int32_t*)vdo.data_ptr());
-    CHECK_HIP_PQ(hipGetLastError());
+    CHECK_HIP(hipGetLastError());
   }
   return {mask, n_valid, vdo};
 }
@@ -1052,14 +1043,14 @@ torch::Tensor pq_expand_codes(torch::Tensor scratch, torch::Tensor pages_blob,
     int block = 256;
     hipLaunchKernelGGL(
         pq_expand_codes_kernel, dim3(pq_grid_waves(n_pages, block)),
-        dim3(block), 0, pq_stream(), (const uint8_t*)scratch.data_ptr(),
+        dim3(block), 0, current_stream(), (const uint8_t*)scratch.data_ptr(),
         (const PageMeta*)pages_blob.data_ptr(), (int)n_pages,
         val_data_off.has_value() ? (const int32_t*)val_data_off->data_ptr()
                                  : nullptr,
         (const int64_t*)dense_off.data_ptr(),
         n_valid.has_value() ? (const int32_t*)n_valid->data_ptr() : nullptr,
         (int32_t*)out.data_ptr());
-    CHECK_HIP_PQ(hipGetLastError());
+    CHECK_HIP(hipGetLastError());
   }
   return out;
 }
@@ -1077,7 +1068,7 @@ torch::Tensor pq_copy_fixed(torch::Tensor scratch, torch::Tensor pages_blob,
     int block = 256;
     int grid = (int)std::min<int64_t>(n_pages, 4096);
     hipLaunchKernelGGL(
-        pq_copy_fixed_kernel, dim3(grid), dim3(block), 0, pq_stream(),
+        pq_copy_fixed_kernel, dim3(grid), dim3(block), 0, current_stream(),
         (const uint8_t*)scratch.data_ptr(),
         (const PageMeta*)pages_blob.data_ptr(), (int)n_pages,
         val_data_off.has_value() ? (const int32_t*)val_data_off->data_ptr()
@@ -1085,7 +1076,7 @@ torch::Tensor pq_copy_fixed(torch::Tensor scratch, torch::Tensor pages_blob,
         (const int64_t*)dense_off.data_ptr(),
         n_valid.has_value() ? (const int32_t*)n_valid->data_ptr() : nullptr,
         (int)esize, (uint8_t*)out.data_ptr());
-    CHECK_HIP_PQ(hipGetLastError());
+    CHECK_HIP(hipGetLastError());
   }
   return out;
 }
@@ -1103,14 +1094,14 @@ std::vector<torch::Tensor> pq_byte_array_lengths(
     int block = 256;
     hipLaunchKernelGGL(
         pq_byte_array_lengths_kernel, dim3(pq_grid_waves(n_pages, block)),
-        dim3(block), 0, pq_stream(), (const uint8_t*)scratch.data_ptr(),
+        dim3(block), 0, current_stream(), (const uint8_t*)scratch.data_ptr(),
         (const PageMeta*)pages_blob.data_ptr(), (int)n_pages,
         val_data_off.has_value() ? (const int32_t*)val_data_off->data_ptr()
                                  : nullptr,
         (const int64_t*)dense_off.data_ptr(),
         n_valid.has_value() ? (const int32_t*)n_valid->data_ptr() : nullptr,
         (int32_t*)lengths.data_ptr(), (int64_t*)src_abs.data_ptr());
-    CHECK_HIP_PQ(hipGetLastError());
+    CHECK_HIP(hipGetLastError());
   }
   return {lengths, src_abs};
 }
@@ -1124,13 +1115,13 @@ torch::Tensor pq_copy_strings(torch::Tensor scratch, torch::Tensor src_abs,
   if (n) {
     int block = 256;
     hipLaunchKernelGGL(pq_copy_strings_kernel, dim3(grid_for(n, block)),
-                       dim3(block), 0, pq_stream(),
+                       dim3(block), 0, current_stream(),
                        (const uint8_t*)scratch.data_ptr(),
                        (const int64_t*)src_abs.data_ptr(),
                        (const int64_t*)dst_off.data_ptr(),
                        (const int32_t*)lengths.data_ptr(), n,
                        (uint8_t*)out.data_ptr());
-    CHECK_HIP_PQ(hipGetLastError());
+    CHECK_HIP(hipGetLastError());
   }
   return out;
 }
@@ -1317,10 +1308,10 @@ std::vector<torch::Tensor> gather_multi(std::vector<torch::Tensor> srcs,
     int block = 256;
     int64_t total = (int64_t)srcs.size() * n;
     hipLaunchKernelGGL(gather_multi_kernel, dim3(grid_for(total, block)),
-                       dim3(block), 0, pq_stream(),
+                       dim3(block), 0, current_stream(),
                        (const GatherCol*)cols_dev.data_ptr(),
                        (int)srcs.size(), (const int64_t*)idx.data_ptr(), n);
-    CHECK_HIP_PQ(hipGetLastError());
+    CHECK_HIP(hipGetLastError());
   }
   return outs;
 }

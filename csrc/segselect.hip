@@ -46,18 +46,11 @@
 
 #include <torch/extension.h>
 #include <ATen/ATen.h>
-#include <c10/hip/HIPStream.h>
 
 #include <algorithm>
 #include <vector>
 
 #include "radix.h"
-
-#define CHECK_HIP_SEG(x)                                                \
-  do {                                                                  \
-    hipError_t e = (x);                                                 \
-    TORCH_CHECK(e == hipSuccess, "HIP error: ", hipGetErrorString(e));  \
-  } while (0)
 
 // keys one lane keeps in registers: 16 u64 are 32 VGPRs
 #define SEG_KPL 16
@@ -140,60 +133,6 @@ DEV_INLINE bool seg_match(uint64_t key, bool first, int hi, uint64_t prefix) {
   return first || (key >> (hi & 63)) == prefix;
 }
 
-// one key into the wave-private histogram; every lane of the wave calls it
-DEV_INLINE void seg_hist_add(uint64_t key, bool match, int shift,
-                             volatile uint32_t* wh, uint64_t ltmask) {
-  const uint32_t d = radix_digit(key, shift, RS_BINS - 1);
-  const uint64_t peers = radix_peers(d, 8, match);
-  if (match && (peers & ltmask) == 0) wh[d] = wh[d] + (uint32_t)__popcll(peers);
-}
-
-struct SegPick {
-  uint32_t digit, left, below, count;
-};
-
-// One wave, lane l holding bins 4l .. 4l+3: the bin that holds `rank`, the
-// rank inside it, the keys in the bins before it and the keys in it.
-DEV_INLINE SegPick seg_wave_pick(const uint32_t c[4], uint32_t rank, int lane) {
-  uint32_t sum = c[0] + c[1] + c[2] + c[3];
-  uint32_t excl = wave_incl_scan(sum, lane) - sum;
-  SegPick p = {0, 0, 0, 0};
-  bool hit = false;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    if (!hit && excl <= rank && rank - excl < c[q]) {
-      hit = true;
-      p.digit = (uint32_t)lane * 4 + q;
-      p.left = rank - excl;
-      p.below = excl;
-      p.count = c[q];
-    }
-    excl += c[q];
-  }
-  const uint64_t m = __ballot(hit);
-  const int src = m ? __ffsll((unsigned long long)m) - 1 : 0;
-  p.digit = __shfl(p.digit, src);
-  p.left = __shfl(p.left, src);
-  p.below = __shfl(p.below, src);
-  p.count = __shfl(p.count, src);
-  return p;
-}
-
-DEV_INLINE uint32_t seg_wave_sum(uint32_t v) {
-#pragma unroll
-  for (int off = WAVE / 2; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
-DEV_INLINE uint64_t seg_wave_min(uint64_t v) {
-#pragma unroll
-  for (int off = WAVE / 2; off > 0; off >>= 1) {
-    uint64_t o = __shfl_xor((unsigned long long)v, off);
-    v = o < v ? o : v;
-  }
-  return v;
-}
-
 // ---------------------------------------------------------------- wave class
 
 template <int WB>
@@ -231,15 +170,15 @@ __global__ __launch_bounds__(RS_THREADS) void seg_wave_kernel(
       for (int j = 0; j < SEG_KPL; ++j) {
         if (j * WAVE < len) {  // the same for every lane
           const bool in = j * WAVE + lane < len;
-          seg_hist_add(k[j], in && seg_match(k[j], p == 0, shift + 8, prefix),
-                       shift, wh, lt);
+          radix_hist_add(in && seg_match(k[j], p == 0, shift + 8, prefix),
+                         k[j], shift, 8, RS_BINS - 1, wh, lt);
         }
       }
       __builtin_amdgcn_wave_barrier();
       uint32_t c[4];
 #pragma unroll
       for (int q = 0; q < 4; ++q) c[q] = wh[lane * 4 + q];
-      const SegPick pk = seg_wave_pick(c, r, lane);
+      const RadixPick pk = radix_wave_pick(c, r, lane);
       prefix = (prefix << 8) | pk.digit;
       r = pk.left;
       below += pk.below;
@@ -253,7 +192,7 @@ __global__ __launch_bounds__(RS_THREADS) void seg_wave_kernel(
       const bool in = j * WAVE + lane < len;
       if (in && k[j] > prefix && k[j] < above) above = k[j];
     }
-    above = seg_wave_min(above);
+    above = wave_min(above);
     const uint32_t upto = below + equal;
     const uint64_t hi = (r0 + 1 < upto || upto >= (uint32_t)len) ? prefix : above;
     if (lane == 0) {
@@ -300,8 +239,8 @@ __global__ __launch_bounds__(RS_THREADS) void seg_block_kernel(
         const int i = m * RS_THREADS + t;
         const bool in = i < len;
         const uint64_t key = in ? sk[i] : 0;
-        seg_hist_add(key, in && seg_match(key, p == 0, shift + 8, prefix),
-                     shift, wh, lt);
+        radix_hist_add(in && seg_match(key, p == 0, shift + 8, prefix), key,
+                       shift, 8, RS_BINS - 1, wh, lt);
       }
       __syncthreads();
       uint32_t c = 0;
@@ -326,7 +265,7 @@ __global__ __launch_bounds__(RS_THREADS) void seg_block_kernel(
       const uint64_t key = sk[i];
       if (key > prefix && key < above) above = key;
     }
-    above = seg_wave_min(above);
+    above = wave_min(above);
     if (lane == 0) wmin[wave] = above;
     __syncthreads();
     if (t == 0) {
@@ -408,13 +347,13 @@ __global__ __launch_bounds__(RS_THREADS) void seg_large_hist_kernel(
       const uint32_t ok = select_load_tile<WB>(src, kind, base, z, aligned, t, k);
 #pragma unroll
       for (int j = 0; j < RS_KPT; ++j)
-        seg_hist_add(k[j], ((ok >> j) & 1u) &&
-                               seg_match(k[j], first, shift + 8, prefix),
-                     shift, wh, lt);
+        radix_hist_add(((ok >> j) & 1u) &&
+                           seg_match(k[j], first, shift + 8, prefix),
+                       k[j], shift, 8, RS_BINS - 1, wh, lt);
     }
     __syncthreads();
     uint32_t c = 0;
-    for (int w = 0; w < RS_WAVES; ++w) {
+    for (int w = 0; w < RS_WAVES; ++w) {  // total and clear in one sweep
       c += hist[w][t];
       hist[w][t] = 0;
     }
@@ -439,7 +378,7 @@ __global__ __launch_bounds__(RS_THREADS) void seg_large_spine_kernel(
       c[q] = g->bins[lane * 4 + q];
       g->bins[lane * 4 + q] = 0;
     }
-    const SegPick pk = seg_wave_pick(c, g->rank, lane);
+    const RadixPick pk = radix_wave_pick(c, g->rank, lane);
     if (lane == 0) {
       g->prefix = (g->prefix << 8) | pk.digit;
       g->rank = pk.left;
@@ -496,8 +435,8 @@ __global__ __launch_bounds__(RS_THREADS) void seg_large_last_kernel(
         if (in && top > prefix && k[j] < hi) hi = k[j];
       }
     }
-    lo = seg_wave_min(lo);
-    hi = seg_wave_min(hi);
+    lo = wave_min(lo);
+    hi = wave_min(hi);
     if (lane == 0) {
       if (lo != ~0ULL) atomicMin((unsigned long long*)&g->lo, (unsigned long long)lo);
       if (hi != ~0ULL) atomicMin((unsigned long long*)&g->hi, (unsigned long long)hi);
@@ -569,7 +508,7 @@ void seg_launch(const SegArgs& a, SegHeader* hdr, SegLarge* st,
                      dim3(grid_for(nslots, RS_THREADS, a.max_blocks)), block, 0,
                      a.stream, (const SegHeader*)hdr, (const SegLarge*)st,
                      nslots, a.nseg, a.kind, a.lo, a.hi);
-  CHECK_HIP_SEG(hipGetLastError());
+  CHECK_HIP(hipGetLastError());
 }
 
 }  // namespace
@@ -583,35 +522,16 @@ int64_t seg_block_keys() { return SEG_BLOCK_KEYS; }
 std::vector<torch::Tensor> seg_select(torch::Tensor keys,
                                       torch::Tensor seg_start,
                                       torch::Tensor rank, int64_t max_blocks) {
-  TORCH_CHECK(keys.is_cuda() && keys.dim() == 1 && keys.is_contiguous(),
-              "seg_select: keys must be a contiguous 1-d device tensor");
-  int kind, wb;
-  switch (keys.scalar_type()) {
-    case torch::kInt8: kind = RK_I8; wb = 1; break;
-    case torch::kInt16: kind = RK_I16; wb = 2; break;
-    case torch::kInt32: kind = RK_I32; wb = 4; break;
-    case torch::kInt64: kind = RK_I64; wb = 8; break;
-    case torch::kUInt8: kind = RK_U8; wb = 1; break;
-    case torch::kFloat32: kind = RK_F32; wb = 4; break;
-    case torch::kFloat64: kind = RK_F64; wb = 8; break;
-    default:
-      TORCH_CHECK(false, "seg_select: unsupported key dtype ",
-                  keys.scalar_type());
-  }
-  auto is_i64 = [&](const torch::Tensor& x) {
-    return x.is_cuda() && x.device() == keys.device() && x.dim() == 1 &&
-           x.is_contiguous() && x.scalar_type() == torch::kInt64;
-  };
-  TORCH_CHECK(is_i64(seg_start) && is_i64(rank),
+  const char* who = "seg_select";
+  const RadixKeys ka = radix_keys_arg(keys, who);
+  TORCH_CHECK(radix_aux_ok(seg_start, keys) && radix_aux_ok(rank, keys),
               "seg_select: seg_start and rank must be contiguous int64 "
               "tensors on the keys' device");
   const int64_t nseg = rank.numel();
   TORCH_CHECK(seg_start.numel() == nseg + 1,
               "seg_select: seg_start must have one entry more than rank");
-  TORCH_CHECK(1 <= max_blocks && max_blocks <= RS_MAX_BLOCKS,
-              "seg_select: max_blocks must be in [1, ", RS_MAX_BLOCKS, "]");
-  const int64_t n = keys.numel();
-  TORCH_CHECK(n < (1LL << 31), "seg_select: 2^31 rows or more");
+  radix_check_max_blocks(max_blocks, who);
+  const int64_t n = ka.n;
   TORCH_CHECK(nseg < (1LL << 31), "seg_select: 2^31 segments or more");
 
   auto lo = torch::zeros({nseg}, keys.options());
@@ -626,8 +546,8 @@ std::vector<torch::Tensor> seg_select(torch::Tensor keys,
   auto state = torch::zeros({nslots * (int64_t)(sizeof(SegLarge) / 8)}, i64);
 
   SegArgs a;
-  a.src = keys.data_ptr();
-  a.kind = kind;
+  a.src = ka.src;
+  a.kind = ka.kind;
   a.n = n;
   a.nseg = nseg;
   a.seg_start = (const int64_t*)seg_start.data_ptr();
@@ -635,14 +555,9 @@ std::vector<torch::Tensor> seg_select(torch::Tensor keys,
   a.lo = lo.data_ptr();
   a.hi = hi.data_ptr();
   a.max_blocks = (int)max_blocks;
-  a.stream = c10::hip::getCurrentHIPStream().stream();
+  a.stream = current_stream();
   SegHeader* hdr = (SegHeader*)header.data_ptr();
   SegLarge* st = (SegLarge*)state.data_ptr();
-  switch (wb) {
-    case 1: seg_launch<1>(a, hdr, st, nslots); break;
-    case 2: seg_launch<2>(a, hdr, st, nslots); break;
-    case 4: seg_launch<4>(a, hdr, st, nslots); break;
-    default: seg_launch<8>(a, hdr, st, nslots); break;
-  }
+  RADIX_DISPATCH_BYTES(ka.width, seg_launch, a, hdr, st, nslots);
   return {lo, hi};
 }

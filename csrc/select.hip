@@ -29,17 +29,10 @@
 
 #include <torch/extension.h>
 #include <ATen/ATen.h>
-#include <c10/hip/HIPStream.h>
 
 #include <algorithm>
 
 #include "radix.h"
-
-#define CHECK_HIP_SELECT(x)                                             \
-  do {                                                                  \
-    hipError_t e = (x);                                                 \
-    TORCH_CHECK(e == hipSuccess, "HIP error: ", hipGetErrorString(e));  \
-  } while (0)
 
 enum SurvivorState : int { SV_NONE = 0, SV_FILL = 1, SV_VALID = 2 };
 
@@ -65,7 +58,7 @@ struct SelectState {
 // than an int8 key column) and bounds a buffer pass at the bytes of one pass
 // over an int64 column's eighth.  A bin above it means the digit barely
 // narrowed the keys, and the next digit gets its chance.
-static int64_t select_cap(int64_t n) {
+int64_t select_capacity(int64_t n) {
   return std::max<int64_t>(n / 8, 1024);
 }
 
@@ -91,9 +84,7 @@ DEV_INLINE void select_hist_tile(const uint64_t k[RS_KPT], uint32_t ok,
   for (int j = 0; j < RS_KPT; ++j) {
     bool valid = (ok >> j) & 1u;
     if (filter) valid = valid && (k[j] >> hi) == prefix;
-    uint32_t d = radix_digit(k[j], shift, dmask);
-    uint64_t peers = radix_peers(d, nbits, valid);
-    if (valid && (peers & lt) == 0) wh[d] = wh[d] + (uint32_t)__popcll(peers);
+    radix_hist_add(valid, k[j], shift, nbits, dmask, wh, lt);
     m[j] = __ballot(valid);
     total += (uint32_t)__popcll(m[j]);
   }
@@ -360,8 +351,6 @@ __global__ __launch_bounds__(RS_THREADS) void select_scatter_kernel(
 
 // ---------------------------------------------------------------- host
 
-int64_t select_capacity(int64_t n) { return select_cap(n); }
-
 namespace {
 
 struct SelectArgs {
@@ -398,7 +387,7 @@ void select_launch(const SelectArgs& a, int64_t k, int width, bool ties_all,
                      k, ties_all, a.nblocks, (const uint32_t*)blk,
                      (const uint32_t*)(blk + a.nblocks), blk + 2 * a.nblocks,
                      blk + 3 * a.nblocks);
-  CHECK_HIP_SELECT(hipGetLastError());
+  CHECK_HIP(hipGetLastError());
 }
 
 }  // namespace
@@ -411,37 +400,19 @@ c10::optional<torch::Tensor> radix_select(torch::Tensor keys, int64_t k,
                                           int64_t begin_bit, int64_t end_bit,
                                           bool ties_all, int64_t max_out,
                                           int64_t max_blocks) {
-  TORCH_CHECK(keys.is_cuda() && keys.dim() == 1 && keys.is_contiguous(),
-              "radix_select: keys must be a contiguous 1-d device tensor");
-  int kind, width;
-  switch (keys.scalar_type()) {
-    case torch::kInt8: kind = RK_I8; width = 8; break;
-    case torch::kInt16: kind = RK_I16; width = 16; break;
-    case torch::kInt32: kind = RK_I32; width = 32; break;
-    case torch::kInt64: kind = RK_I64; width = 64; break;
-    case torch::kUInt8: kind = RK_U8; width = 8; break;
-    case torch::kFloat32: kind = RK_F32; width = 32; break;
-    case torch::kFloat64: kind = RK_F64; width = 64; break;
-    default:
-      TORCH_CHECK(false, "radix_select: unsupported key dtype ",
-                  keys.scalar_type());
-  }
-  const int wb = width / 8;
-  if (end_bit < 0) end_bit = width;
-  TORCH_CHECK(0 <= begin_bit && begin_bit < end_bit && end_bit <= 64,
-              "radix_select: bad bit range [", begin_bit, ", ", end_bit, ")");
-  TORCH_CHECK(1 <= max_blocks && max_blocks <= RS_MAX_BLOCKS,
-              "radix_select: max_blocks must be in [1, ", RS_MAX_BLOCKS, "]");
-  const int64_t n = keys.numel();
-  TORCH_CHECK(n < (1LL << 31), "radix_select: 2^31 rows or more");
+  const char* who = "radix_select";
+  const RadixKeys ka = radix_keys_arg(keys, who);
+  end_bit = radix_end_bit(begin_bit, end_bit, ka.width, who);
+  radix_check_max_blocks(max_blocks, who);
+  const int64_t n = ka.n;
   TORCH_CHECK(1 <= k && k < n, "radix_select: k must be in [1, n)");
   if (max_out < 0) max_out = n;
 
   auto i64 = torch::dtype(torch::kInt64).device(keys.device());
   auto i32 = torch::dtype(torch::kInt32).device(keys.device());
   SelectArgs a;
-  a.src = keys.data_ptr();
-  a.kind = kind;
+  a.src = ka.src;
+  a.kind = ka.kind;
   a.n = n;
   a.tiles = (n + RS_TILE - 1) / RS_TILE;
   a.aligned = ((uintptr_t)a.src & 15) == 0;
@@ -449,9 +420,9 @@ c10::optional<torch::Tensor> radix_select(torch::Tensor keys, int64_t k,
   const int sel_width = (int)(end_bit - begin_bit);
   a.wmask = sel_width == 64 ? ~0ULL : (1ULL << sel_width) - 1ULL;
   a.nblocks = (int)std::min<int64_t>(max_blocks, a.tiles);
-  a.stream = c10::hip::getCurrentHIPStream().stream();
+  a.stream = current_stream();
 
-  const int64_t cap = select_cap(n);
+  const int64_t cap = select_capacity(n);
   static_assert(sizeof(SelectState) % 8 == 0, "state is a whole int64 tensor");
   auto state = torch::zeros({(int64_t)(sizeof(SelectState) / 8)}, i64);
   auto buf = torch::empty({cap}, i64);
@@ -459,12 +430,8 @@ c10::optional<torch::Tensor> radix_select(torch::Tensor keys, int64_t k,
   SelectState* st = (SelectState*)state.data_ptr();
   uint64_t* bufp = (uint64_t*)buf.data_ptr();
   uint32_t* blkp = (uint32_t*)blk.data_ptr();
-  switch (wb) {
-    case 1: select_launch<1>(a, k, sel_width, ties_all, bufp, cap, st, blkp); break;
-    case 2: select_launch<2>(a, k, sel_width, ties_all, bufp, cap, st, blkp); break;
-    case 4: select_launch<4>(a, k, sel_width, ties_all, bufp, cap, st, blkp); break;
-    default: select_launch<8>(a, k, sel_width, ties_all, bufp, cap, st, blkp); break;
-  }
+  RADIX_DISPATCH_BYTES(ka.width, select_launch, a, k, sel_width, ties_all, bufp,
+                       cap, st, blkp);
 
   int64_t out_n = k;
   if (ties_all) {
@@ -484,6 +451,6 @@ c10::optional<torch::Tensor> radix_select(torch::Tensor keys, int64_t k,
                      (const uint32_t*)(blkp + 2 * a.nblocks),
                      (const uint32_t*)(blkp + 3 * a.nblocks),
                      (int64_t*)out.data_ptr(), out_n);
-  CHECK_HIP_SELECT(hipGetLastError());
+  CHECK_HIP(hipGetLastError());
   return out;
 }

@@ -21,17 +21,10 @@
 
 #include <torch/extension.h>
 #include <ATen/ATen.h>
-#include <c10/hip/HIPStream.h>
 
 #include <algorithm>
 
 #include "radix.h"
-
-#define CHECK_HIP_SORT(x)                                               \
-  do {                                                                  \
-    hipError_t e = (x);                                                 \
-    TORCH_CHECK(e == hipSuccess, "HIP error: ", hipGetErrorString(e));  \
-  } while (0)
 
 #define RS_SCAN_THREADS 1024
 
@@ -76,12 +69,9 @@ __global__ __launch_bounds__(RS_THREADS) void radix_count_kernel(
       k[j] = i < r.end ? keys[i] : 0;
     }
 #pragma unroll
-    for (int j = 0; j < RS_KPT; ++j) {
-      bool valid = base + j * RS_THREADS + t < r.end;
-      uint32_t d = radix_digit(k[j], shift, dmask);
-      uint64_t peers = radix_peers(d, nbits, valid);
-      if (valid && (peers & lt) == 0) wh[d] = wh[d] + (uint32_t)__popcll(peers);
-    }
+    for (int j = 0; j < RS_KPT; ++j)
+      radix_hist_add(base + j * RS_THREADS + t < r.end, k[j], shift, nbits,
+                     dmask, wh, lt);
   }
   __syncthreads();
   uint32_t s = 0;
@@ -248,46 +238,27 @@ torch::Tensor radix_argsort(torch::Tensor keys, int64_t begin_bit,
                             int64_t end_bit,
                             c10::optional<torch::Tensor> perm,
                             int64_t max_blocks) {
-  TORCH_CHECK(keys.is_cuda() && keys.dim() == 1 && keys.is_contiguous(),
-              "radix_argsort: keys must be a contiguous 1-d device tensor");
-  int kind, width;
-  switch (keys.scalar_type()) {
-    case torch::kInt8: kind = RK_I8; width = 8; break;
-    case torch::kInt16: kind = RK_I16; width = 16; break;
-    case torch::kInt32: kind = RK_I32; width = 32; break;
-    case torch::kInt64: kind = RK_I64; width = 64; break;
-    case torch::kUInt8: kind = RK_U8; width = 8; break;
-    case torch::kFloat32: kind = RK_F32; width = 32; break;
-    case torch::kFloat64: kind = RK_F64; width = 64; break;
-    default:
-      TORCH_CHECK(false, "radix_argsort: unsupported key dtype ",
-                  keys.scalar_type());
-  }
-  if (end_bit < 0) end_bit = width;
-  TORCH_CHECK(0 <= begin_bit && begin_bit < end_bit && end_bit <= 64,
-              "radix_argsort: bad bit range [", begin_bit, ", ", end_bit, ")");
-  TORCH_CHECK(1 <= max_blocks && max_blocks <= RS_MAX_BLOCKS,
-              "radix_argsort: max_blocks must be in [1, ", RS_MAX_BLOCKS, "]");
-  const int64_t n_src = keys.numel();
-  int64_t n = n_src;
+  const char* who = "radix_argsort";
+  const RadixKeys ka = radix_keys_arg(keys, who);
+  end_bit = radix_end_bit(begin_bit, end_bit, ka.width, who);
+  radix_check_max_blocks(max_blocks, who);
+  int64_t n = ka.n;
   const int64_t* perm_p = nullptr;
   if (perm.has_value()) {
     const torch::Tensor& p = *perm;
-    TORCH_CHECK(p.is_cuda() && p.device() == keys.device() && p.dim() == 1 &&
-                    p.is_contiguous() && p.scalar_type() == torch::kInt64,
+    TORCH_CHECK(radix_aux_ok(p, keys),
                 "radix_argsort: perm must be a contiguous int64 tensor on "
                 "the keys' device");
     n = p.numel();
     perm_p = (const int64_t*)p.data_ptr();
+    TORCH_CHECK(n < (1LL << 31), "radix_argsort: 2^31 rows or more");
   }
-  TORCH_CHECK(n < (1LL << 31) && n_src < (1LL << 31),
-              "radix_argsort: 2^31 rows or more");
   auto i64 = torch::dtype(torch::kInt64).device(keys.device());
   auto i32 = torch::dtype(torch::kInt32).device(keys.device());
   auto out = torch::empty({n}, i64);
   if (n == 0) return out;
 
-  hipStream_t stream = c10::hip::getCurrentHIPStream().stream();
+  hipStream_t stream = current_stream();
   const int64_t tiles = (n + RS_TILE - 1) / RS_TILE;
   const int nblocks = (int)std::min<int64_t>(max_blocks, tiles);
   torch::Tensor kbuf[2] = {torch::empty({n}, i64), torch::empty({n}, i64)};
@@ -295,10 +266,10 @@ torch::Tensor radix_argsort(torch::Tensor keys, int64_t begin_bit,
   auto counts = torch::empty({(int64_t)RS_BINS * nblocks}, i32);
 
   hipLaunchKernelGGL(radix_keys_kernel, dim3(grid_for(n, RS_THREADS)),
-                     dim3(RS_THREADS), 0, stream, keys.data_ptr(), kind, n_src,
+                     dim3(RS_THREADS), 0, stream, ka.src, ka.kind, ka.n,
                      perm_p, n, (uint64_t*)kbuf[0].data_ptr(),
                      (uint32_t*)ibuf[0].data_ptr());
-  CHECK_HIP_SORT(hipGetLastError());
+  CHECK_HIP(hipGetLastError());
 
   int cur = 0;
   for (int64_t bit = begin_bit; bit < end_bit; bit += 8) {
@@ -318,7 +289,7 @@ torch::Tensor radix_argsort(torch::Tensor keys, int64_t begin_bit,
         (uint32_t*)ibuf[cur ^ 1].data_ptr(),
         last ? (int64_t*)out.data_ptr() : (int64_t*)nullptr, n, tiles,
         (int)bit, nbits, (const uint32_t*)counts.data_ptr());
-    CHECK_HIP_SORT(hipGetLastError());
+    CHECK_HIP(hipGetLastError());
     cur ^= 1;
   }
   return out;

@@ -30,12 +30,12 @@
 
 #include <torch/extension.h>
 #include <ATen/ATen.h>
-#include <c10/hip/HIPStream.h>
 
 #include <algorithm>
 #include <cstring>
 
 #include "common.h"
+#include "hip_host.h"
 
 #define SM_THREADS 256
 #define SM_WAVES (SM_THREADS / WAVE)
@@ -272,10 +272,9 @@ torch::Tensor string_match(torch::Tensor bytes, torch::Tensor offsets,
 
   const int64_t tiles = (n + SM_TILE - 1) / SM_TILE;
   const int nblocks = (int)std::min<int64_t>(max_blocks, tiles);
-  hipStream_t stream = c10::hip::getCurrentHIPStream().stream();
+  hipStream_t stream = current_stream();
   hipLaunchKernelGGL(string_match_kernel, dim3(nblocks), dim3(SM_THREADS), 0,
                      stream, a);
-  hipError_t e = hipGetLastError();
-  TORCH_CHECK(e == hipSuccess, "string_match: ", hipGetErrorString(e));
+  check_launch("string_match");
   return out;
 }

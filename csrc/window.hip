@@ -29,13 +29,13 @@
 
 #include <torch/extension.h>
 #include <ATen/ATen.h>
-#include <c10/hip/HIPStream.h>
 
 #include <algorithm>
 #include <type_traits>
 #include <vector>
 
 #include "common.h"
+#include "hip_host.h"
 
 #define SS_THREADS 256
 #define SS_WAVES (SS_THREADS / WAVE)
@@ -513,7 +513,7 @@ std::vector<torch::Tensor> seg_scan(torch::Tensor values,
   if (want_count) outs.push_back(torch::empty({n}, i64));
   if (n == 0) return outs;
 
-  hipStream_t stream = c10::hip::getCurrentHIPStream().stream();
+  hipStream_t stream = current_stream();
   const int64_t tiles = (n + SS_TILE - 1) / SS_TILE;
   const int nblocks = (int)std::min<int64_t>(max_blocks, tiles);
   auto table = torch::empty({5 * (int64_t)nblocks}, i64);
@@ -543,8 +543,7 @@ std::vector<torch::Tensor> seg_scan(torch::Tensor values,
     SEG_SCAN_CASE(SS_MAX_F64)
   }
 #undef SEG_SCAN_CASE
-  hipError_t e = hipGetLastError();
-  TORCH_CHECK(e == hipSuccess, "seg_scan: ", hipGetErrorString(e));
+  check_launch("seg_scan");
   return outs;
 }
 
@@ -565,7 +564,7 @@ std::vector<torch::Tensor> seg_window_combine(
   auto out = torch::empty_like(P);
   auto inv = torch::empty({n}, torch::dtype(torch::kUInt8).device(P.device()));
   if (n == 0) return {out, inv};
-  hipStream_t stream = c10::hip::getCurrentHIPStream().stream();
+  hipStream_t stream = current_stream();
   hipLaunchKernelGGL(seg_window_combine_kernel, dim3(grid_for(n, 256)),
                      dim3(256), 0, stream, (const double*)P.data_ptr(),
                      (const double*)S.data_ptr(), (const int64_t*)pc.data_ptr(),
@@ -573,7 +572,6 @@ std::vector<torch::Tensor> seg_window_combine(
                      (const int64_t*)row_in_seg.data_ptr(), w,
                      is_max ? 1 : 0, n, (double*)out.data_ptr(),
                      (uint8_t*)inv.data_ptr());
-  hipError_t e = hipGetLastError();
-  TORCH_CHECK(e == hipSuccess, "seg_window_combine: ", hipGetErrorString(e));
+  check_launch("seg_window_combine");
   return {out, inv};
 }
