@@ -242,7 +242,12 @@ FUSED_LDS_BYTES = 48 * 1024
 # Dense (direct-address) groupby: when the keys' known ranges bound the key
 # space, the mixed-radix key is the group's slot and one kernel reads keys
 # and values and updates the accumulators (groupby_dense_fused).
-# BODO_AMD_DENSE_GROUPBY=0 turns the route off.
+# BODO_AMD_DENSE_GROUPBY=0 turns the route off.  Inside groupby_dense_fused
+# the extension itself chooses between its atomic kernel and partitioning
+# the rows by slot range with LDS aggregation; it reads
+# BODO_AMD_DENSE_PARTITION on every call: 0 keeps the atomic kernel, unset
+# or 1 partitions large tables with many rows, force partitions whenever
+# the aggregates allow it.
 DENSE_GROUPBY = os.environ.get("BODO_AMD_DENSE_GROUPBY", "1") != "0"
 DENSE_MAX_KEYS = 8
 DENSE_MAX_SLOTS = 1 << 25

@@ -16,13 +16,16 @@
 #include <torch/extension.h>
 #include <ATen/ATen.h>
 
+#include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <vector>
 
 #include "common.h"
+#include "dense_partition.h"
 #include "hip_host.h"
 #include "parquet.h"
+#include "radix.h"
 
 // ---------------------------------------------------------------------
 // ColumnDesc marshalling
@@ -1055,6 +1058,531 @@ __global__ void dense_gather_kernel(const uint64_t* __restrict__ table,
   }
 }
 
+// ---------------------------------------------------------------------
+// Partitioned route of the dense groupby.  The atomic kernel above sends
+// every row's updates to a table that is larger than every cache.  This
+// route computes each row's slot once, brings the rows of S consecutive
+// slots (a partition, dense_partition.h) together with stable LSD radix
+// passes over the partition id, aggregates each partition in one block's
+// LDS and writes its table words with plain stores.
+//
+// A record is a 32-bit word (slot in the low 25 bits, above them one
+// invalid bit per aggregate, bit 31 "skip this row") and one 8-byte value
+// word per aggregate that folds a value (not SIZE, not COUNT), kept as
+// separate arrays that scatter by the same ranks.  The first pass reads
+// the values from the source columns in row order.
+// ---------------------------------------------------------------------
+
+static_assert(DP_TILE == RS_TILE && DP_MAX_BLOCKS == RS_MAX_BLOCKS,
+              "dense_partition.h repeats two constants of radix.h");
+static_assert(DENSE_MAX_SLOTS == (int64_t(1) << DP_SLOT_BITS), "");
+static_assert(DP_SLOT_BITS + MAX_FUSED_AGGS < 31, "record word layout");
+
+#define DP_SLOT_MASK ((1u << DP_SLOT_BITS) - 1u)
+#define DP_SKIP (1u << 31)
+#define DP_BINS (1 << DP_PASS_BITS)
+#define DP_MAX_VALS 2
+// record loads a thread keeps in flight in the aggregation
+#define DP_UNROLL 4
+
+struct DensePartVals {
+  const uint64_t* in[DP_MAX_VALS];  // nullptr: read the source column
+  uint64_t* out[DP_MAX_VALS];
+  int agg[DP_MAX_VALS];         // the aggregate of a value word
+  int vidx[MAX_FUSED_AGGS];     // the value word of an aggregate, or -1
+  int nvals;
+};
+
+struct DensePartTable {
+  uint64_t* table;
+  uint64_t init[MAX_FUSED_AGGS];
+  int64_t nslots;
+  int64_t partitions;
+  int part_bits;
+};
+
+DEV_INLINE bool dpart_carries(uint32_t w, int k) {  // valid row and value
+  return (w & (DP_SKIP | (1u << (DP_SLOT_BITS + k)))) == 0;
+}
+
+DEV_INLINE int64_t dpart_partition(uint32_t w, const DensePartTable& t) {
+  int64_t p = (w & DP_SLOT_MASK) >> t.part_bits;
+  return p < t.partitions ? p : t.partitions - 1;
+}
+
+// the value word of aggregate a at source row i
+DEV_INLINE uint64_t dpart_value(const DenseAgg& a, int64_t i) {
+  AggValue v = agg_load(a.col, i);
+  return is_f64_acc(a.op) ? (uint64_t)__double_as_longlong(v.dv)
+                          : (uint64_t)v.iv;
+}
+
+// value word v of the record at position i whose word is w
+DEV_INLINE uint64_t dpart_load_value(const DenseAggs& aggs,
+                                     const DensePartVals& vals, int v,
+                                     uint32_t w, int64_t i) {
+  if (vals.in[v] != nullptr) return vals.in[v][i];
+  return dpart_carries(w, vals.agg[v]) ? dpart_value(aggs.a[vals.agg[v]], i)
+                                       : 0ull;
+}
+
+// Slot pass.  A key outside its range sets the error word as the atomic
+// kernel does; its record is a skip word with slot bits zero, so it can
+// index nothing outside the table or a partition.
+__global__ void dense_part_slot_kernel(const DenseKeys keys,
+                                       const DenseAggs aggs,
+                                       uint32_t* __restrict__ words,
+                                       int64_t* __restrict__ err, int64_t n) {
+  GRID_STRIDE_LOOP(i, n) {
+    uint64_t slot = 0;
+    bool in_range = true;
+    for (int k = 0; k < keys.nkeys; ++k) {
+      uint64_t digit = (uint64_t)load_int_key(keys.data[k], keys.dtype[k], i) -
+                       (uint64_t)keys.lo[k];
+      in_range &= digit < keys.radix[k];
+      slot += digit * keys.stride[k];
+    }
+    if (!in_range) {
+      *err = 1;
+      words[i] = DP_SKIP;
+      continue;
+    }
+    uint32_t w = (uint32_t)slot & DP_SLOT_MASK;
+    for (int k = 0; k < aggs.n_aggs; ++k) {
+      if (aggs.a[k].op == AGG_SIZE) continue;
+      if (!agg_load(aggs.a[k].col, i).valid) w |= 1u << (DP_SLOT_BITS + k);
+    }
+    words[i] = w;
+  }
+}
+
+// counts[digit * nblocks + block], as radix_count_kernel, for record words
+__global__ __launch_bounds__(RS_THREADS) void dense_part_count_kernel(
+    const uint32_t* __restrict__ words, int64_t n, int64_t tiles, int shift,
+    int nbits, uint32_t* __restrict__ counts) {
+  __shared__ uint32_t hist[RS_WAVES][DP_BINS];
+  const int t = threadIdx.x, lane = t % WAVE, wave = t / WAVE;
+  const uint32_t dmask = (1u << nbits) - 1u;
+  const uint64_t lt = (1ULL << lane) - 1ULL;
+  if (t < DP_BINS)
+    for (int w = 0; w < RS_WAVES; ++w) hist[w][t] = 0;
+  __syncthreads();
+  RadixRange r = radix_block_range(n, tiles, gridDim.x, blockIdx.x);
+  volatile uint32_t* wh = hist[wave];
+  for (int64_t base = r.begin; base < r.end; base += RS_TILE) {
+    uint32_t k[RS_KPT];
+#pragma unroll
+    for (int j = 0; j < RS_KPT; ++j) {
+      int64_t i = base + j * RS_THREADS + t;
+      k[j] = i < r.end ? words[i] : 0;
+    }
+#pragma unroll
+    for (int j = 0; j < RS_KPT; ++j)
+      radix_hist_add(base + j * RS_THREADS + t < r.end, k[j], shift, nbits,
+                     dmask, wh, lt);
+  }
+  __syncthreads();
+  if (t <= (int)dmask) {
+    uint32_t s = 0;
+    for (int w = 0; w < RS_WAVES; ++w) s += hist[w][t];
+    counts[(int64_t)t * gridDim.x + blockIdx.x] = s;
+  }
+}
+
+// One stable pass, as radix_scatter_kernel: rank in the wave by ballots,
+// wave counts to tile-local digit starts, the tile's records to their
+// sorted place in LDS, then runs of equal digits out to global memory.
+template <int NV>
+__global__ __launch_bounds__(RS_THREADS) void dense_part_scatter_kernel(
+    const uint32_t* __restrict__ words_in, uint32_t* __restrict__ words_out,
+    const DenseAggs aggs, const DensePartVals vals, int64_t n, int64_t tiles,
+    int shift, int nbits, const uint32_t* __restrict__ offsets) {
+  __shared__ uint32_t s_words[RS_TILE];
+  __shared__ uint64_t s_vals[NV ? NV : 1][RS_TILE];
+  __shared__ uint32_t s_wcnt[RS_WAVES][DP_BINS];
+  __shared__ uint32_t s_base[DP_BINS];
+  __shared__ uint32_t s_start[DP_BINS];
+  __shared__ uint32_t s_wsum[RS_WAVES];
+  const int t = threadIdx.x, lane = t % WAVE, wave = t / WAVE;
+  const uint32_t dmask = (1u << nbits) - 1u;
+  const uint64_t lt = (1ULL << lane) - 1ULL;
+  const bool owner = t <= (int)dmask;  // thread t owns digit t
+  RadixRange r = radix_block_range(n, tiles, gridDim.x, blockIdx.x);
+  if (t < DP_BINS)
+    s_base[t] = owner ? offsets[(int64_t)t * gridDim.x + blockIdx.x] : 0;
+  volatile uint32_t* wc = s_wcnt[wave];
+  uint32_t tile_total = 0;
+
+  for (int64_t base = r.begin; base < r.end; base += RS_TILE) {
+    if (t < DP_BINS) s_base[t] += tile_total;
+    for (int j = 0; j < DP_BINS / WAVE; ++j) wc[j * WAVE + lane] = 0;
+
+    const int64_t slice = base + (int64_t)wave * (WAVE * RS_KPT);
+    uint32_t k[RS_KPT];
+    uint64_t x[NV ? NV : 1][RS_KPT];
+    uint32_t off[RS_KPT];
+#pragma unroll
+    for (int j = 0; j < RS_KPT; ++j) {
+      int64_t i = slice + j * WAVE + lane;
+      bool valid = i < r.end;
+      k[j] = valid ? words_in[i] : 0;
+#pragma unroll
+      for (int v = 0; v < NV; ++v)
+        x[v][j] = valid ? dpart_load_value(aggs, vals, v, k[j], i) : 0ull;
+    }
+#pragma unroll
+    for (int j = 0; j < RS_KPT; ++j) {
+      bool valid = slice + j * WAVE + lane < r.end;
+      uint32_t d = radix_digit(k[j], shift, dmask);
+      uint64_t peers = radix_peers(d, nbits, valid);
+      uint32_t rank = (uint32_t)__popcll(peers & lt);
+      uint32_t old = valid ? wc[d] : 0;
+      if (valid && rank == 0) wc[d] = old + (uint32_t)__popcll(peers);
+      off[j] = old + rank;
+    }
+    __syncthreads();
+
+    uint32_t c[RS_WAVES];
+    uint32_t total = 0;
+#pragma unroll
+    for (int w = 0; w < RS_WAVES; ++w) {
+      c[w] = t < DP_BINS ? s_wcnt[w][t] : 0;
+      total += c[w];
+    }
+    uint32_t inc = wave_incl_scan(total, lane);
+    if (lane == WAVE - 1) s_wsum[wave] = inc;
+    __syncthreads();
+    uint32_t start = inc - total;
+    for (int w = 0; w < wave; ++w) start += s_wsum[w];
+    if (t < DP_BINS) {
+      s_start[t] = start;
+      uint32_t run = start;
+#pragma unroll
+      for (int w = 0; w < RS_WAVES; ++w) {
+        s_wcnt[w][t] = run;
+        run += c[w];
+      }
+    }
+    tile_total = total;
+    __syncthreads();
+
+#pragma unroll
+    for (int j = 0; j < RS_KPT; ++j) {
+      if (slice + j * WAVE + lane < r.end) {
+        uint32_t d = radix_digit(k[j], shift, dmask);
+        uint32_t pos = s_wcnt[wave][d] + off[j];
+        if (pos < RS_TILE) {
+          s_words[pos] = k[j];
+#pragma unroll
+          for (int v = 0; v < NV; ++v) s_vals[v][pos] = x[v][j];
+        }
+      }
+    }
+    __syncthreads();
+
+    const int tile_n = (int)(r.end - base < RS_TILE ? r.end - base : RS_TILE);
+#pragma unroll
+    for (int j = 0; j < RS_KPT; ++j) {
+      int pos = j * RS_THREADS + t;
+      if (pos < tile_n) {
+        uint32_t w = s_words[pos];
+        uint32_t d = radix_digit(w, shift, dmask);
+        int64_t dst = (int64_t)s_base[d] + (pos - (int)s_start[d]);
+        if (dst >= 0 && dst < n) {  // holds whenever the counts match
+          words_out[dst] = w;
+#pragma unroll
+          for (int v = 0; v < NV; ++v) vals.out[v][dst] = s_vals[v][pos];
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// part_off[p] = first position of partition p in the sorted records,
+// part_off[partitions] = n: each position fills the entries of the
+// partitions that begin at it.
+__global__ void dense_part_offsets_kernel(const uint32_t* __restrict__ words,
+                                          const DensePartTable tbl,
+                                          uint32_t* __restrict__ part_off,
+                                          int64_t n) {
+  GRID_STRIDE_LOOP(i, n) {
+    int64_t cur = dpart_partition(words[i], tbl);
+    int64_t prev = i ? dpart_partition(words[i - 1], tbl) : -1;
+    for (int64_t p = prev + 1; p <= cur; ++p) part_off[p] = (uint32_t)i;
+    if (i == n - 1)
+      for (int64_t p = cur + 1; p <= tbl.partitions; ++p)
+        part_off[p] = (uint32_t)n;
+  }
+}
+
+// rows [r0, r1) of partition p, both inside [0, n) whatever part_off holds
+DEV_INLINE void dpart_rows(const uint32_t* __restrict__ part_off, int64_t p,
+                           int64_t n, int64_t* r0, int64_t* r1) {
+  int64_t b = part_off[p + 1], a = part_off[p];
+  *r1 = b < n ? b : n;
+  *r0 = a < *r1 ? a : *r1;
+}
+
+DEV_INLINE void dpart_lds_init(uint64_t* s_acc, uint32_t* s_inv, int n_aggs,
+                               int S, const DensePartTable& tbl) {
+  const int words = 1 + n_aggs;
+  for (int j = threadIdx.x; j < S * words; j += RS_THREADS) {
+    int w = j % words;
+    s_acc[j] = w == 0 ? 0ull : tbl.init[w - 1];
+  }
+  for (int j = threadIdx.x; j < S * n_aggs; j += RS_THREADS) s_inv[j] = 0;
+}
+
+// records [lo, hi), all of one partition, into the LDS accumulators
+DEV_INLINE void dpart_accumulate(const uint32_t* __restrict__ words,
+                                 const DenseAggs& aggs,
+                                 const DensePartVals& vals, int64_t lo,
+                                 int64_t hi, uint64_t* s_acc, uint32_t* s_inv,
+                                 int S) {
+  const int nw = 1 + aggs.n_aggs;
+  for (int64_t base = lo; base < hi; base += DP_UNROLL * RS_THREADS) {
+    uint32_t w[DP_UNROLL];
+    uint64_t x[DP_MAX_VALS][DP_UNROLL];
+#pragma unroll
+    for (int j = 0; j < DP_UNROLL; ++j) {
+      int64_t i = base + j * RS_THREADS + threadIdx.x;
+      w[j] = i < hi ? words[i] : DP_SKIP;
+    }
+#pragma unroll
+    for (int j = 0; j < DP_UNROLL; ++j) {
+      int64_t i = base + j * RS_THREADS + threadIdx.x;
+#pragma unroll
+      for (int v = 0; v < DP_MAX_VALS; ++v)
+        x[v][j] = v < vals.nvals && !(w[j] & DP_SKIP)
+                      ? dpart_load_value(aggs, vals, v, w[j], i) : 0ull;
+    }
+#pragma unroll
+    for (int j = 0; j < DP_UNROLL; ++j) {
+      if (w[j] & DP_SKIP) continue;
+      const int s = (int)(w[j] & (uint32_t)(S - 1));
+      atomicAdd((unsigned long long*)&s_acc[s * nw], 1ull);
+      for (int k = 0; k < aggs.n_aggs; ++k) {
+        int op = aggs.a[k].op;
+        if (op == AGG_SIZE) continue;
+        if (!dpart_carries(w[j], k)) {
+          atomicAdd(&s_inv[k * S + s], 1u);
+          continue;
+        }
+        int v = vals.vidx[k];
+        if (v < 0) continue;  // COUNT
+        uint64_t bits = v == 0 ? x[0][j] : x[1][j];
+        agg_apply(op, (double*)&s_acc[s * nw + 1 + k],
+                  __longlong_as_double((long long)bits), (int64_t)bits, 0);
+      }
+    }
+  }
+}
+
+// Block p aggregates partition p and writes every table word and invalid
+// count of its slots with plain stores.  A partition of more rows than
+// chunk_cap only gets its init values here: dense_part_split_kernel adds
+// its rows.
+__global__ __launch_bounds__(RS_THREADS) void dense_part_agg_kernel(
+    const uint32_t* __restrict__ words, const DenseAggs aggs,
+    const DensePartVals vals, const DensePartTable tbl,
+    const uint32_t* __restrict__ part_off, int64_t chunk_cap, int64_t n) {
+  __shared__ uint64_t s_acc[DP_ACC_WORDS];
+  __shared__ uint32_t s_inv[DP_INV_WORDS];
+  const int S = 1 << tbl.part_bits;
+  const int nw = 1 + aggs.n_aggs;
+  const int64_t p = blockIdx.x;
+  int64_t r0, r1;
+  dpart_rows(part_off, p, n, &r0, &r1);
+  dpart_lds_init(s_acc, s_inv, aggs.n_aggs, S, tbl);
+  __syncthreads();
+  if (r1 - r0 <= chunk_cap)
+    dpart_accumulate(words, aggs, vals, r0, r1, s_acc, s_inv, S);
+  __syncthreads();
+  const int64_t slot0 = p * S;
+  for (int j = threadIdx.x; j < S * nw; j += RS_THREADS)
+    if (slot0 + j / nw < tbl.nslots) tbl.table[slot0 * nw + j] = s_acc[j];
+  for (int k = 0; k < aggs.n_aggs; ++k) {
+    if (aggs.a[k].invalid == nullptr) continue;
+    for (int s = threadIdx.x; s < S; s += RS_THREADS)
+      if (slot0 + s < tbl.nslots)
+        aggs.a[k].invalid[slot0 + s] = (int64_t)s_inv[k * S + s];
+  }
+}
+
+// Block j takes the sorted records [j * chunk_cap, (j + 1) * chunk_cap).
+// A partition of more than chunk_cap rows that reaches into them holds
+// their first or their last record; the block aggregates its share of such
+// a partition in LDS and merges the slots it touched into the table, which
+// dense_part_agg_kernel has initialised, with global atomics.
+__global__ __launch_bounds__(RS_THREADS) void dense_part_split_kernel(
+    const uint32_t* __restrict__ words, const DenseAggs aggs,
+    const DensePartVals vals, const DensePartTable tbl,
+    const uint32_t* __restrict__ part_off, int64_t chunk_cap, int64_t n) {
+  __shared__ uint64_t s_acc[DP_ACC_WORDS];
+  __shared__ uint32_t s_inv[DP_INV_WORDS];
+  const int S = 1 << tbl.part_bits;
+  const int nw = 1 + aggs.n_aggs;
+  const int64_t lo = blockIdx.x * chunk_cap;
+  if (lo >= n) return;
+  const int64_t hi = lo + chunk_cap < n ? lo + chunk_cap : n;
+  const int64_t p_first = dpart_partition(words[lo], tbl);
+  const int64_t p_last = dpart_partition(words[hi - 1], tbl);
+  for (int side = 0; side < 2; ++side) {
+    if (side == 1 && p_last == p_first) break;
+    const int64_t p = side ? p_last : p_first;
+    int64_t r0, r1;
+    dpart_rows(part_off, p, n, &r0, &r1);
+    if (r1 - r0 <= chunk_cap) continue;
+    const int64_t a = lo > r0 ? lo : r0, b = hi < r1 ? hi : r1;
+    if (a >= b) continue;
+    dpart_lds_init(s_acc, s_inv, aggs.n_aggs, S, tbl);
+    __syncthreads();
+    dpart_accumulate(words, aggs, vals, a, b, s_acc, s_inv, S);
+    __syncthreads();
+    for (int s = threadIdx.x; s < S; s += RS_THREADS) {
+      const uint64_t c = s_acc[s * nw];
+      const int64_t slot = p * S + s;
+      if (c == 0 || slot >= tbl.nslots) continue;
+      uint64_t* row = tbl.table + slot * nw;
+      atomicAdd((unsigned long long*)row, (unsigned long long)c);
+      for (int k = 0; k < aggs.n_aggs; ++k) {
+        int op = aggs.a[k].op;
+        if (op == AGG_SIZE) continue;
+        uint32_t inv = s_inv[k * S + s];
+        if (inv != 0 && aggs.a[k].invalid != nullptr)
+          atomicAdd((unsigned long long*)&aggs.a[k].invalid[slot],
+                    (unsigned long long)inv);
+        uint64_t bits = s_acc[s * nw + 1 + k];
+        agg_apply(op, (double*)(row + 1 + k),
+                  __longlong_as_double((long long)bits), (int64_t)bits, 0);
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// BODO_AMD_DENSE_PARTITION: "0" keeps the atomic kernel, "force" takes the
+// partitioned route whenever the aggregates allow it, unset or anything
+// else takes it above the thresholds below.
+enum DensePartMode : int { DP_MODE_OFF, DP_MODE_AUTO, DP_MODE_FORCE };
+
+static DensePartMode dense_partition_mode() {
+  const char* e = getenv("BODO_AMD_DENSE_PARTITION");
+  if (e == nullptr) return DP_MODE_AUTO;
+  if (strcmp(e, "0") == 0) return DP_MODE_OFF;
+  if (strcmp(e, "force") == 0) return DP_MODE_FORCE;
+  return DP_MODE_AUTO;
+}
+
+// Thresholds of the automatic choice (profiles/dense_partition.md §2): from
+// 2^24 rows on the partitioned route's slowest call beat the atomic
+// kernel's fastest at every table size measured, 1.5 MiB being the smallest;
+// at 2^22 rows it lost on tables of 386 MB and more.
+#define DP_MIN_TABLE_BYTES (int64_t(3) << 19)
+#define DP_MIN_ROWS (int64_t(1) << 24)
+
+static bool dense_use_partition(const std::vector<int64_t>& ops,
+                                int64_t nslots, int64_t n) {
+  DensePartMode mode = dense_partition_mode();
+  if (mode == DP_MODE_OFF || n >= (int64_t(1) << 31)) return false;
+  int nvals = 0;
+  for (int64_t op : ops) {
+    if (op < AGG_SUM_F64 || op > AGG_SIZE) return false;  // no LDS form
+    if (op != AGG_SIZE && op != AGG_COUNT) ++nvals;
+  }
+  if (nvals > DP_MAX_VALS) return false;
+  if (mode == DP_MODE_FORCE) return true;
+  int64_t table_bytes = nslots * (1 + (int64_t)ops.size()) * 8;
+  return table_bytes >= DP_MIN_TABLE_BYTES && n >= DP_MIN_ROWS;
+}
+
+// Fills table (and the invalid arrays of aggs) from uninitialised memory.
+static void dense_partitioned_fill(const DenseKeys& keys, const DenseAggs& aggs,
+                                   const uint64_t* init_bits, int64_t nslots,
+                                   int64_t n, torch::Tensor& table,
+                                   torch::Tensor& err) {
+  auto dev = table.device();
+  auto i64 = torch::dtype(torch::kInt64).device(dev);
+  auto i32 = torch::dtype(torch::kInt32).device(dev);
+  hipStream_t stream = current_stream();
+  const DensePartGeom g = dense_part_geometry(nslots, 1 + aggs.n_aggs, n);
+
+  DensePartVals vals = {};
+  for (int k = 0; k < aggs.n_aggs; ++k) {
+    int op = aggs.a[k].op;
+    vals.vidx[k] = -1;
+    if (op == AGG_SIZE || op == AGG_COUNT) continue;
+    vals.vidx[k] = vals.nvals;
+    vals.agg[vals.nvals++] = k;
+  }
+  DensePartTable tbl = {};
+  tbl.table = (uint64_t*)table.data_ptr();
+  for (int k = 0; k < aggs.n_aggs; ++k) tbl.init[k] = init_bits[k];
+  tbl.nslots = nslots;
+  tbl.partitions = g.partitions;
+  tbl.part_bits = g.part_bits;
+
+  torch::Tensor wbuf[2] = {torch::empty({n}, i32), torch::Tensor()};
+  torch::Tensor vbuf[2][DP_MAX_VALS];
+  hipLaunchKernelGGL(dense_part_slot_kernel, dim3(grid_for(n, 256)), dim3(256),
+                     0, stream, keys, aggs, (uint32_t*)wbuf[0].data_ptr(),
+                     (int64_t*)err.data_ptr(), n);
+  CHECK_HIP(hipGetLastError());
+
+  int cur = 0;
+  if (g.passes > 0) {
+    wbuf[1] = torch::empty({n}, i32);
+    auto counts = torch::empty({(int64_t)DP_BINS * g.radix_blocks + 4}, i32);
+    for (int p = 0; p < g.passes; ++p) {
+      const int bins = 1 << g.pass_bits[p];
+      const int total = (bins * g.radix_blocks + 3) / 4 * 4;
+      for (int v = 0; v < vals.nvals; ++v) {
+        if (!vbuf[cur ^ 1][v].defined())
+          vbuf[cur ^ 1][v] = torch::empty({n}, i64);
+        vals.in[v] = p == 0 ? nullptr
+                            : (const uint64_t*)vbuf[cur][v].data_ptr();
+        vals.out[v] = (uint64_t*)vbuf[cur ^ 1][v].data_ptr();
+      }
+      hipLaunchKernelGGL(dense_part_count_kernel, dim3(g.radix_blocks),
+                         dim3(RS_THREADS), 0, stream,
+                         (const uint32_t*)wbuf[cur].data_ptr(), n, g.tiles,
+                         g.pass_shift[p], g.pass_bits[p],
+                         (uint32_t*)counts.data_ptr());
+      radix_scan_counts((uint32_t*)counts.data_ptr(), total, stream);
+      const uint32_t* win = (const uint32_t*)wbuf[cur].data_ptr();
+      uint32_t* wout = (uint32_t*)wbuf[cur ^ 1].data_ptr();
+      const uint32_t* offs = (const uint32_t*)counts.data_ptr();
+#define DP_SCATTER(NV)                                                       \
+  hipLaunchKernelGGL(dense_part_scatter_kernel<NV>, dim3(g.radix_blocks),    \
+                     dim3(RS_THREADS), 0, stream, win, wout, aggs, vals, n,  \
+                     g.tiles, g.pass_shift[p], g.pass_bits[p], offs)
+      if (vals.nvals == 0) DP_SCATTER(0);
+      else if (vals.nvals == 1) DP_SCATTER(1);
+      else DP_SCATTER(2);
+#undef DP_SCATTER
+      CHECK_HIP(hipGetLastError());
+      cur ^= 1;
+    }
+  }
+  for (int v = 0; v < vals.nvals; ++v)
+    vals.in[v] = g.passes > 0 ? (const uint64_t*)vbuf[cur][v].data_ptr()
+                              : nullptr;
+
+  const uint32_t* sorted = (const uint32_t*)wbuf[cur].data_ptr();
+  auto part_off = torch::zeros({g.partitions + 1}, i32);
+  hipLaunchKernelGGL(dense_part_offsets_kernel, dim3(grid_for(n, 256)),
+                     dim3(256), 0, stream, sorted, tbl,
+                     (uint32_t*)part_off.data_ptr(), n);
+  hipLaunchKernelGGL(dense_part_agg_kernel, dim3((unsigned)g.single_items),
+                     dim3(RS_THREADS), 0, stream, sorted, aggs, vals, tbl,
+                     (const uint32_t*)part_off.data_ptr(), g.chunk_cap, n);
+  hipLaunchKernelGGL(dense_part_split_kernel, dim3((unsigned)g.split_items),
+                     dim3(RS_THREADS), 0, stream, sorted, aggs, vals, tbl,
+                     (const uint32_t*)part_off.data_ptr(), g.chunk_cap, n);
+  CHECK_HIP(hipGetLastError());
+}
+
 // Returns {} when a key fell outside its [lo, lo + radix): nothing of the
 // result is valid then.  Otherwise [slot_ids, acc_0, cnt_0, acc_1, ...]:
 // slot_ids int64 [ngroups], and per aggregate what agg_update_fused returns
@@ -1100,6 +1628,8 @@ std::vector<torch::Tensor> groupby_dense_fused(
   aggs.n_aggs = n_aggs;
   uint64_t init_bits[MAX_FUSED_AGGS] = {};
   std::vector<torch::Tensor> invalids(n_aggs);
+  // the partitioned route writes every table word and invalid count itself
+  const bool partitioned = dense_use_partition(ops, nslots, n);
   for (int k = 0; k < n_aggs; ++k) {
     TORCH_CHECK(ops[k] >= AGG_SUM_F64 && ops[k] <= AGG_SIZE,
                 "groupby_dense_fused: unsupported op ", ops[k]);
@@ -1117,8 +1647,9 @@ std::vector<torch::Tensor> groupby_dense_fused(
                  dtypes[k] == BT_FLOAT64;
     }
     if (nullable) {
-      invalids[k] = torch::zeros({nslots},
-                                 torch::dtype(torch::kInt64).device(dev));
+      auto i64 = torch::dtype(torch::kInt64).device(dev);
+      invalids[k] = partitioned ? torch::empty({nslots}, i64)
+                                : torch::zeros({nslots}, i64);
       aggs.a[k].invalid = (int64_t*)invalids[k].data_ptr();
     }
     if (is_f64_acc(ops[k])) {
@@ -1132,15 +1663,21 @@ std::vector<torch::Tensor> groupby_dense_fused(
   auto table = torch::empty({nslots * words}, i64);
   auto err = torch::zeros({1}, i64);
   int block = 256;
-  hipLaunchKernelGGL(dense_init_kernel, dim3(grid_for(nslots * words, block)),
-                     dim3(block), 0, current_stream(),
-                     (uint64_t*)table.data_ptr(), words, init_bits[0],
-                     init_bits[1], init_bits[2], init_bits[3], nslots);
-  CHECK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(groupby_dense_fused_kernel, dim3(grid_for(n, block)),
-                     dim3(block), 0, current_stream(), keys, aggs,
-                     (uint64_t*)table.data_ptr(), (int64_t*)err.data_ptr(), n);
-  CHECK_HIP(hipGetLastError());
+  if (partitioned) {
+    dense_partitioned_fill(keys, aggs, init_bits, nslots, n, table, err);
+  } else {
+    hipLaunchKernelGGL(dense_init_kernel,
+                       dim3(grid_for(nslots * words, block)), dim3(block), 0,
+                       current_stream(), (uint64_t*)table.data_ptr(), words,
+                       init_bits[0], init_bits[1], init_bits[2], init_bits[3],
+                       nslots);
+    CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(groupby_dense_fused_kernel, dim3(grid_for(n, block)),
+                       dim3(block), 0, current_stream(), keys, aggs,
+                       (uint64_t*)table.data_ptr(), (int64_t*)err.data_ptr(),
+                       n);
+    CHECK_HIP(hipGetLastError());
+  }
   DenseSlots view{(const uint64_t*)table.data_ptr(), words};
   auto groups = compact_slots(view, nslots, dev, /*want_slot_gid=*/false, &err);
   if (groups.extra != 0) return {};

@@ -236,6 +236,10 @@ inline RadixKeys radix_keys_arg(const torch::Tensor& keys, const char* who) {
   return k;
 }
 
+// In-place exclusive scan of a digit-major count table on one block
+// (sort.hip).  total is a multiple of 4 and the table is 16-byte aligned.
+void radix_scan_counts(uint32_t* counts, int total, hipStream_t stream);
+
 inline void radix_check_max_blocks(int64_t max_blocks, const char* who) {
   TORCH_CHECK(1 <= max_blocks && max_blocks <= RS_MAX_BLOCKS, who,
               ": max_blocks must be in [1, ", RS_MAX_BLOCKS, "]");

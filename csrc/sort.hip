@@ -117,6 +117,11 @@ __global__ __launch_bounds__(RS_SCAN_THREADS) void radix_scan_kernel(
   }
 }
 
+void radix_scan_counts(uint32_t* counts, int total, hipStream_t stream) {
+  hipLaunchKernelGGL(radix_scan_kernel, dim3(1), dim3(RS_SCAN_THREADS), 0,
+                     stream, counts, total);
+}
+
 // ---------------------------------------------------------------- scatter
 
 // Block b walks its tiles in order.  base[d] is where the block's next key
@@ -278,9 +283,7 @@ torch::Tensor radix_argsort(torch::Tensor keys, int64_t begin_bit,
     hipLaunchKernelGGL(radix_count_kernel, dim3(nblocks), dim3(RS_THREADS), 0,
                        stream, (const uint64_t*)kbuf[cur].data_ptr(), n, tiles,
                        (int)bit, nbits, (uint32_t*)counts.data_ptr());
-    hipLaunchKernelGGL(radix_scan_kernel, dim3(1), dim3(RS_SCAN_THREADS), 0,
-                       stream, (uint32_t*)counts.data_ptr(),
-                       RS_BINS * nblocks);
+    radix_scan_counts((uint32_t*)counts.data_ptr(), RS_BINS * nblocks, stream);
     hipLaunchKernelGGL(
         radix_scatter_kernel, dim3(nblocks), dim3(RS_THREADS), 0, stream,
         (const uint64_t*)kbuf[cur].data_ptr(),
