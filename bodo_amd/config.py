@@ -68,6 +68,11 @@ KERNEL_CACHE_DIR = os.environ.get(
 #: gfx950 kernel of csrc/strmatch.hip on a GPU; off = arrow compute on host
 STRING_MATCH = _env_bool("BODO_AMD_STRING_MATCH", True)
 
+#: len / lower / upper / strip / lstrip / rstrip / slice and || on plain
+#: string columns run the gfx950 kernels of csrc/strxform.hip on a GPU; off =
+#: arrow compute or a pandas object series on host
+STRING_TRANSFORM = _env_bool("BODO_AMD_STRING_TRANSFORM", True)
+
 #: Limit(Sort) finds its k rows with the radix select of csrc/select.hip on
 #: a GPU ("0": a full sort, then the first k); ops/gpu.py reads the same
 #: variable into TOPK_SELECT, which is what the route consults

@@ -170,9 +170,13 @@ class _Evaluator:
 
     def _concat(self, e: BinOp) -> Column:
         """String concatenation (SQL || / CONCAT).  DICT column + string
-        constant stays device-resident (dictionary transform); other
-        combinations concatenate on host."""
+        constant stays device-resident (dictionary transform), and so do
+        plain string columns on a GPU with each other or with a constant
+        (csrc/strxform.hip); other combinations concatenate on host."""
         import pyarrow as pa
+
+        from . import gpu
+        from .. import config
 
         for col_e, const_e, right in ((e.left, e.right, True),
                                       (e.right, e.left, False)):
@@ -187,11 +191,19 @@ class _Evaluator:
                                   dictionary=pa.array(
                                       vals, type=pa.large_string()),
                                   length=len(a))
+                if config.STRING_TRANSFORM and _plain_device_string(a) and \
+                        gpu.string_concat_eligible(cv.encode()):
+                    return gpu.string_concat(a, cv.encode()) if right \
+                        else gpu.string_concat(cv.encode(), a)
                 sa = a.to_pandas().astype(object)
                 res = (sa + cv) if right else (cv + sa)
                 return Column.from_arrow(pa.Array.from_pandas(res),
                                          self.device)
         a, b = self.visit(e.left), self.visit(e.right)
+        if config.STRING_TRANSFORM and _plain_device_string(a) and \
+                _plain_device_string(b) and len(a) == len(b) and \
+                a.device == b.device:
+            return gpu.string_concat(a, b)
         sa = a.to_pandas().astype(object)
         sb = b.to_pandas().astype(object)
         return Column.from_arrow(pa.Array.from_pandas(sa + sb), self.device)
@@ -1129,6 +1141,13 @@ def _device_string_match(a: Column, op: str, pat: str) -> Optional[Column]:
     return Column(bt.boolean, out, a.mask)
 
 
+def _plain_device_string(a: Column) -> bool:
+    """A plain string (not binary) column on a GPU: what csrc/strxform.hip
+    transforms."""
+    return a.is_cuda and a.dtype.kind == TypeKind.STRING and \
+        a.dtype.precision != 1
+
+
 def str_op(a: Column, op: str, args, kwargs=None) -> Column:
     import pyarrow.compute as pc
 
@@ -1206,6 +1225,14 @@ def str_op(a: Column, op: str, args, kwargs=None) -> Column:
         out = _device_string_match(a, op, args[0])
         if out is not None:
             return out
+    if config.STRING_TRANSFORM and not kwargs and _plain_device_string(a):
+        from . import gpu
+
+        if gpu.string_transform_eligible(op, args):
+            # None: the column needs Unicode tables, which are below
+            out = gpu.string_transform(a, op, args)
+            if out is not None:
+                return out
     # plain strings: arrow compute on host
     arr = a.to_arrow() if not a.is_cuda else a.to_device("cpu").to_arrow()
     fmap = {

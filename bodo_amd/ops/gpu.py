@@ -1283,6 +1283,140 @@ def string_match(col: Column, segments, anchor_start: bool, anchor_end: bool,
     return out.view(torch.bool)
 
 
+# Transforms of plain string columns (csrc/strxform.hip).
+STRXFORM_MEASURE_OPS = {"len": 0, "strip": 1, "lstrip": 2, "rstrip": 3,
+                        "slice": 4}
+STRXFORM_OPS = frozenset(STRXFORM_MEASURE_OPS) | {"lower", "upper"}
+STRXFORM_MAX_LITERAL_BYTES = 256
+
+
+def _is_int(x) -> bool:
+    return isinstance(x, (int, np.integer)) and not isinstance(x, bool)
+
+
+def string_transform_eligible(op: str, args=()) -> bool:
+    """The kernels take `op` with `args`: strip / lstrip / rstrip without a
+    character set, slice(start[, stop[, step]]) with integer or None bounds
+    and step 1, and len / lower / upper."""
+    if op not in STRXFORM_OPS:
+        return False
+    if op == "slice":
+        return 1 <= len(args) <= 3 and \
+            all(x is None or _is_int(x) for x in args[:2]) and \
+            (len(args) < 3 or args[2] is None or
+             (_is_int(args[2]) and args[2] == 1))
+    if op in ("strip", "lstrip", "rstrip"):
+        return all(x is None for x in args)
+    return not args
+
+
+def string_concat_eligible(literal: bytes) -> bool:
+    return len(literal) <= STRXFORM_MAX_LITERAL_BYTES
+
+
+def _plain_gpu_string(col) -> bool:
+    return isinstance(col, Column) and col.dtype.kind == TypeKind.STRING \
+        and col.is_cuda
+
+
+def _string_buffers(col: Column):
+    """(bytes, offsets, mask as uint8) of a plain string column, contiguous.
+    The offsets index the bytes as they stand, so a first offset other than
+    zero needs nothing."""
+    data, mask8 = _data_mask8(col)
+    if data is None:
+        data = torch.zeros(0, dtype=torch.uint8, device=col.device)
+    return data.contiguous(), col.offsets.contiguous(), \
+        None if mask8 is None else mask8.contiguous()
+
+
+_NO_LITERAL = torch.zeros(0, dtype=torch.uint8)
+
+
+def string_transform(col: Column, op: str, args=(),
+                     max_blocks: int = 2048) -> Optional[Column]:
+    """`op` (with `args`; see string_transform_eligible) over the rows of a
+    plain string column on a GPU, null rows staying null.
+
+    len is one launch and no host synchronisation.  Every other op reads one
+    small tensor back once, the output's byte count and the fallback flag
+    together (for lower / upper the flag alone): that read is its single
+    host synchronisation.  The flag is up when the answer may need Unicode
+    tables, that is a trim that stopped at a byte >= 0x80 or a case map that
+    met one; the result is then None and the caller takes the host route."""
+    if not _plain_gpu_string(col):
+        raise ValueError("string_transform takes a plain string column on a GPU")
+    if not string_transform_eligible(op, args):
+        raise ValueError(f"string_transform does not take {op}{tuple(args)}")
+    data, offsets, mask8 = _string_buffers(col)
+    n = len(col)
+    if op == "len":
+        out = kernels().string_measure(
+            data, offsets, mask8, 0, max_blocks=max_blocks)[0]
+        return Column(bt.int64, out, col.mask)
+    if op in ("lower", "upper"):
+        out, flag = kernels().string_case(data, op == "upper", max_blocks)
+        if data.numel() and flag.item():
+            return None
+        return Column(col.dtype, out, col.mask, offsets=col.offsets, length=n)
+    start = stop = None
+    if op == "slice":
+        start = args[0]
+        stop = args[1] if len(args) > 1 else None
+    out_off, begin, flag = kernels().string_measure(
+        data, offsets, mask8, STRXFORM_MEASURE_OPS[op], int(start or 0),
+        int(stop or 0), stop is not None, max_blocks)
+    total = 0
+    if n:
+        out_off[1:].cumsum_(0)
+        total, fallback = torch.stack((out_off[-1], flag[0])).tolist()
+        if fallback:
+            return None
+    out = kernels().string_build(out_off, total, data, offsets, begin, None,
+                                 None, _NO_LITERAL, max_blocks)
+    return Column(col.dtype, out, col.mask, offsets=out_off, length=n)
+
+
+def string_concat(a, b, max_blocks: int = 2048) -> Column:
+    """Row i is a[i] ++ b[i], null where either is null.  Each side is a
+    plain string column on a GPU or `bytes` of at most
+    STRXFORM_MAX_LITERAL_BYTES, and one side at least is a column.  One host
+    synchronisation, the read of the output's byte count."""
+    is_lit = [isinstance(x, (bytes, bytearray)) for x in (a, b)]
+    cols = [x for x, lit in zip((a, b), is_lit) if not lit]
+    if not cols or not all(_plain_gpu_string(c) for c in cols):
+        raise ValueError("string_concat takes plain string columns on a GPU "
+                         "and at most one bytes literal")
+    if len(cols) == 2 and (len(a) != len(b) or a.device != b.device):
+        raise ValueError("string_concat takes columns of one length on one "
+                         "device")
+    literal = b"".join(bytes(x) for x, lit in zip((a, b), is_lit) if lit)
+    if not string_concat_eligible(literal):
+        raise ValueError(f"string_concat takes a literal of at most "
+                         f"{STRXFORM_MAX_LITERAL_BYTES} bytes")
+    n = len(cols[0])
+    masks = [c.mask for c in cols if c.mask is not None]
+    mask = None if not masks else masks[0] if len(masks) == 1 \
+        else masks[0] & masks[1]
+    mask8 = None if mask is None else mask.view(torch.uint8).contiguous()
+    (a_bytes, a_off), (b_bytes, b_off) = [
+        (None, None) if lit else _string_buffers(x)[:2]
+        for x, lit in zip((a, b), is_lit)]
+    out_off = kernels().string_concat_measure(
+        a_off, 0 if a_bytes is None else a_bytes.numel(),
+        b_off, 0 if b_bytes is None else b_bytes.numel(),
+        len(literal), mask8, max_blocks)
+    total = 0
+    if n:
+        out_off[1:].cumsum_(0)
+        total = int(out_off[-1])
+    lit = torch.frombuffer(bytearray(literal), dtype=torch.uint8) \
+        if literal else _NO_LITERAL
+    out = kernels().string_build(out_off, total, a_bytes, a_off, None,
+                                 b_bytes, b_off, lit, max_blocks)
+    return Column(cols[0].dtype, out, mask, offsets=out_off, length=n)
+
+
 def take_table_fused(tbl: Table, idx: torch.Tensor) -> Optional[Table]:
     """All fixed-width columns (+masks) of a take materialize in ONE kernel
     launch (join-heavy queries were launch-bound on per-column

@@ -2075,6 +2075,30 @@ torch::Tensor string_match(torch::Tensor bytes, torch::Tensor offsets,
                            int64_t max_blocks);
 int64_t strmatch_lds_bytes();
 
+// strxform.hip: len / strip / slice / case / concat on plain string columns
+std::vector<torch::Tensor> string_measure(torch::Tensor bytes,
+                                          torch::Tensor offsets,
+                                          c10::optional<torch::Tensor> mask,
+                                          int64_t op, int64_t start,
+                                          int64_t stop, bool has_stop,
+                                          int64_t max_blocks);
+torch::Tensor string_concat_measure(c10::optional<torch::Tensor> a_offsets,
+                                    int64_t a_nbytes,
+                                    c10::optional<torch::Tensor> b_offsets,
+                                    int64_t b_nbytes, int64_t lit_len,
+                                    c10::optional<torch::Tensor> mask,
+                                    int64_t max_blocks);
+torch::Tensor string_build(torch::Tensor out_offsets, int64_t total,
+                           c10::optional<torch::Tensor> a_bytes,
+                           c10::optional<torch::Tensor> a_offsets,
+                           c10::optional<torch::Tensor> a_begin,
+                           c10::optional<torch::Tensor> b_bytes,
+                           c10::optional<torch::Tensor> b_offsets,
+                           torch::Tensor literal, int64_t max_blocks);
+std::vector<torch::Tensor> string_case(torch::Tensor bytes, bool upper,
+                                       int64_t max_blocks);
+int64_t strxform_lds_bytes();
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_f32", &gemm_f32, "f32 MFMA GEMM (v_mfma_f32_16x16x4_f32)");
   m.def("rle_expand", &rle_expand, "parquet RLE/bit-packed hybrid expand");
@@ -2169,5 +2193,31 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("segs"), py::arg("seg_ends"), py::arg("anchor_start"),
         py::arg("anchor_end"), py::arg("max_blocks") = 2048);
   m.attr("STRMATCH_LDS_BYTES") = strmatch_lds_bytes();
+  m.def("string_measure", &string_measure,
+        "op 0 len -> [code points per row]; 1 strip, 2 lstrip, 3 rstrip, "
+        "4 slice(start, stop) -> [0 and the output byte lengths (n + 1), "
+        "first source byte per row, fallback flag]",
+        py::arg("bytes"), py::arg("offsets"), py::arg("mask"), py::arg("op"),
+        py::arg("start") = 0, py::arg("stop") = 0,
+        py::arg("has_stop") = false, py::arg("max_blocks") = 2048);
+  m.def("string_concat_measure", &string_concat_measure,
+        "0 and the byte lengths of a[i] ++ b[i] (n + 1); a side without "
+        "offsets is the literal of lit_len bytes; 0 where mask is 0",
+        py::arg("a_offsets"), py::arg("a_nbytes"), py::arg("b_offsets"),
+        py::arg("b_nbytes"), py::arg("lit_len"), py::arg("mask"),
+        py::arg("max_blocks") = 2048);
+  m.def("string_build", &string_build,
+        "the bytes of rows out_offsets describes: row i is the part of A "
+        "from a_begin[i] (or its whole row), then B's row; a side without "
+        "bytes is the literal (host uint8)",
+        py::arg("out_offsets"), py::arg("total"), py::arg("a_bytes"),
+        py::arg("a_offsets"), py::arg("a_begin"), py::arg("b_bytes"),
+        py::arg("b_offsets"), py::arg("literal"),
+        py::arg("max_blocks") = 2048);
+  m.def("string_case", &string_case,
+        "ASCII lower / upper of a byte buffer -> [bytes, flag: a byte >= "
+        "0x80 was met]",
+        py::arg("bytes"), py::arg("upper"), py::arg("max_blocks") = 2048);
+  m.attr("STRXFORM_LDS_BYTES") = strxform_lds_bytes();
   m.attr("_native") = true;
 }

@@ -18,7 +18,8 @@ setup(
             name="bodo_amd_kernels",
             sources=["csrc/kernels.hip", "csrc/gemm.hip", "csrc/parquet.hip",
                      "csrc/sort.hip", "csrc/window.hip", "csrc/strmatch.hip",
-                     "csrc/select.hip", "csrc/segselect.hip"],
+                     "csrc/strxform.hip", "csrc/select.hip",
+                     "csrc/segselect.hip"],
             extra_compile_args={
                 "cxx": ["-O3", "-std=c++17"],
                 "nvcc": ["-O3", "-std=c++17", "--offload-arch=gfx950"],
